@@ -12,18 +12,20 @@ visibility MLP), 8+8 BRDF-lobe visibility samples, SG shading (128 direct + 24 i
 outputs.  Synthetic weights (robir_amd.synth, seed 0), random draws generated on the device inside the step.
 One step = ONE such image rendered by all N GPUs together ("strong": rank r renders chunks {c : c mod N = r} of the view,
 robir_amd.parallel.render_view_sharded, and the 17-float tiles are all-gathered over RCCL at the end of the step -- the
-partition SURVEY.md 8e / north_star name).  `value` = rays of that image / step time.  For N > 1 a secondary figure times the
-weak form (rank r renders its own view r).  The octree build is one-off set-up and is reported separately.
+partition SURVEY.md 8e / north_star name).  `value` = rays of that image / step time.  With `--full` and N > 1 a secondary figure
+times the weak form (rank r renders its own view r).  The octree build is one-off set-up and is reported separately.
 
 Arithmetic (`--precision`): the headline is `exact` -- NOT narrower than the reference's fp32: the light-visibility MLP (98 % of
 the FLOPs) carries every fp32 operand exactly as three f16 pieces and forms the six partial products of weight >= 2^-22 on the
-f16 MFMA in three fp32 accumulators (csrc/vis_diffuse_x6.hip), every other MLP runs on the f32-input MFMA.  At N = 1 the line
-also carries `legs` (the same view on the f32-input MFMA everywhere, and in split precision = 22-bit operand pairs, each
+f16 MFMA in three fp32 accumulators (csrc/vis_diffuse_x6.hip), every other MLP runs on the f32-input MFMA.  With `--full` at N = 1
+the line also carries `legs` (the same view on the f32-input MFMA everywhere, and in split precision = 22-bit operand pairs, each
 timed over its own loop, with image distances) and `configs` (BASELINE configs 1, 2, 3, 5; `--config N` prints one of them as
 its own line).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: fused light-SG visibility, MFMA bound) and, at
-N=1, `cpu_baseline` (the oracle restatement timed on this box's host cores on a bounded sample of the same workload).
+Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: fused light-SG visibility, MFMA bound, from HIP events around its
+launches in the timed steps) and, with `--full` at N=1, `cpu_baseline` (the oracle restatement timed on this box's host cores on a
+bounded sample of the same workload).  A plain run sets up, warms up, times the --steps steps, writes the last step's image under
+`--dump-outputs DIR` if given, and prints the line; everything else runs only under `--full`.
 """
 import argparse
 import json
@@ -50,6 +52,7 @@ TRAFFIC_B_PER_PAIR = {"f16x6": 33.0, "f16x1": 68.4, "default": 22.1}
 TRAFFIC_PROFILE = {"f16x1": "profiles/r05_dvis_f16p_pmc.md"}
 H = W = 800
 CHUNK = 1024
+STEP_SEED = 20260928                # torch's CPU and device generators are set to this at the start of every step
 
 
 PRECISIONS = {
@@ -110,7 +113,20 @@ def parse():
                     help="light / BRDF-lobe visibility model: the visibility MLP (default, the reference's default) or traced "
                          "visibility = OctreeVisModel(octree_ray_tracer), the reference's `trace_vis` switch "
                          "(training/train_pbr.py:409-410): the MLP's 98 %% of the PBR FLOPs become octree gathers")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the RCCL self-check (N = 1), package power during the timed steps, the "
+                         "side legs in the other precisions, the other scene, the `configs` / `extras` figures and the CPU baseline (N = 1), "
+                         "the weak-scaling views and the collective alone (N > 1).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image the last timed step rendered as DIR/<field>.npy (float32, [H, W, "
+                         "channels], the fields of robir_amd.parallel.TILE_FIELDS; 43.5 MB in all).  Every step draws its random numbers "
+                         "from the same seed, so the same arguments give the same inputs run after run")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 4:
+        ap.error("--dump-outputs writes the headline workload's image (--config 4)")
+    return args
 
 
 def view_pose(rank, distance=0.9):
@@ -300,6 +316,20 @@ def emit(line):
     out.flush()
 
 
+def dump_outputs(d, image):
+    """The image of the last timed step, [H*W, 17] as render_view_sharded returns it, one float32 array [H, W, c] per field."""
+    from robir_amd import parallel
+    os.makedirs(d, exist_ok=True)
+    img = image.float().cpu().numpy()
+    widths = {"roughness": 1, "network_object_mask": 1}
+    a = 0
+    for name in parallel.TILE_FIELDS:
+        c = widths.get(name, 3)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(img[:, a:a + c].reshape(H, W, c)))
+        a += c
+    assert a == img.shape[1] == 17, (a, img.shape)
+
+
 def runner_loop_replay(model, uv_d, pose_d, K_d, hdr, chunk=1024):
     """train_pbr.py:248-285 in its own shape: per 1024-pixel chunk one forward(), a few tone-mapped / detached fields kept, merged, read."""
     from robir_amd import deferred
@@ -378,7 +408,7 @@ def main():
     if world > 1:
         import torch.distributed as dist
         parallel.init_distributed(backend, dev)
-    elif backend == "nccl" and os.environ.get("ROBIR_RCCL_SELFCHECK", "1") == "1":
+    elif args.full and backend == "nccl" and os.environ.get("ROBIR_RCCL_SELFCHECK", "1") == "1":
         # one GPU: run the tile gather once through RCCL with a process group of one rank (outside the timed region), so that the line
         # says whether the collective backend of the multi-GPU path loads and runs on this box
         rccl_check = rccl_selfcheck(parallel, dev)
@@ -430,7 +460,9 @@ def main():
     plan = parallel.plan_view(H * W, CHUNK, dev, interleave=True, chunks_per_pass=args.chunks_per_batch)
 
     def step():
-        """One image: this rank's chunks (all of them at N = 1), then the all-gather of the tiles -> [H*W, 17] on every rank."""
+        """One image: this rank's chunks (all of them at N = 1), then the all-gather of the tiles -> [H*W, 17] on every rank.
+        Every step draws its random numbers from the same seed: the image does not depend on how many steps ran before it."""
+        torch.manual_seed(STEP_SEED)
         return parallel.render_view_sharded(model, uv_d, pose_d, K_d, hdr, CHUNK, stats=stats, plan=plan)
 
     def barrier():
@@ -487,7 +519,7 @@ def main():
     barrier()
     stats.clear()
     timer.on = True
-    power = PowerProbe() if rank == 0 else None      # package power while the timed steps run (rocm-smi, best effort)
+    power = PowerProbe() if rank == 0 and args.full else None      # package power while the timed steps run (rocm-smi, best effort)
     dt, out = timed(step, args.steps, tag="step")
     power_line = power.stop() if power is not None else None
     timer.on = False
@@ -496,6 +528,8 @@ def main():
     hit_frac = float(out[:, 16].mean())
     evals = int(stats["diffuse_vis_evals"]) if "diffuse_vis_evals" in stats else 0
     k_ms, k_n = timer.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     per_rank = allgather_ms = None
     if world > 1:
@@ -514,12 +548,13 @@ def main():
             allr = host
         per_rank = [{"rank": r, "chunks": int(v[0]), "step_ms": float(v[1]), "dvis_kernel_ms_per_step": float(v[2]),
                      "visibility_pairs_per_step": float(v[3])} for r, v in enumerate(allr)]
-        # the collective alone: the padded tile gather of one view (what the end of every step does), timed over 5 repetitions
-        per = (plan["n_chunks"] + world - 1) // world
-        pad = torch.zeros(per * CHUNK, 17, device=dev)
-        parallel.all_gather_tiles(pad)
-        t_ag, _ = timed(lambda: parallel.all_gather_tiles(pad), 5)
-        allgather_ms = t_ag / 5 * 1e3
+        if args.full:
+            # the collective alone: the padded tile gather of one view (what the end of every step does), timed over 5 repetitions
+            per = (plan["n_chunks"] + world - 1) // world
+            pad = torch.zeros(per * CHUNK, 17, device=dev)
+            parallel.all_gather_tiles(pad)
+            t_ag, _ = timed(lambda: parallel.all_gather_tiles(pad), 5)
+            allgather_ms = t_ag / 5 * 1e3
         # the roofline of an N-rank line is the SLOWEST rank's kernel time over that rank's own pairs (rank 0's alone would mislead)
         slow = max(per_rank, key=lambda r: r["dvis_kernel_ms_per_step"])
         if slow["dvis_kernel_ms_per_step"] > 0 and k_n > 0:
@@ -527,7 +562,7 @@ def main():
             k_ms, evals = slow["dvis_kernel_ms_per_step"] / launches_per_step, int(slow["visibility_pairs_per_step"] * args.steps)
 
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         # secondary figure: the weak form (rank r renders its own whole view r, tiles all-gathered)
         pose_r = torch.from_numpy(view_pose(rank)).to(dev)
         plan1 = dict(parallel.plan_view(H * W, CHUNK, dev), world=1)
@@ -600,14 +635,15 @@ def main():
             # syncs + the tile gather): what the first SCALE run is held against
             base_ms = {"exact": 1260.0, "f16": 338.0, "split": 700.0, "fp32-mfma": 3650.0}.get(args.precision)
             line["per_rank"] = per_rank
-            line["allgather_ms"] = allgather_ms
+            if allgather_ms is not None:
+                line["allgather_ms"] = allgather_ms
             line["roofline"]["of_rank"] = max(per_rank, key=lambda r: r["dvis_kernel_ms_per_step"])["rank"]
             line["roofline"]["note_ranks"] = "kernel time and pair count of the SLOWEST rank (max over ranks of the per-step kernel time)"
             if base_ms is not None:
                 line["predicted_ms_per_step"] = {"value": base_ms * math.ceil(625 / world) / 625 + 2.0 + 0.43 * (world - 1) / world,
                                                  "source": "DESIGN.md section 7: single-GPU step x ceil(625/N)/625 + ~2 ms per pass + tile gather at ~100 GB/s per "
                                                            "xGMI link; ranks sharing one GPU (functional runs) are NOT expected to meet it"}
-    if world == 1 and not args.no_legs and args.vis == "mlp":
+    if args.full and world == 1 and not args.no_legs and args.vis == "mlp":
         # Side legs, each timed over its own loop: the same view and the same random draws in the other two precisions, and the
         # distance of every image from the f32-input-MFMA one (|a-b| / (|b| + mean|b|) over the 17 channels of all rays).
         images, legs = {}, {}
@@ -650,7 +686,7 @@ def main():
                              "bitwise the f32-input MFMA's sums), so the entries beyond 1e-4 are rays on which a threshold decision -- "
                              "a sampled direction on the n.d > 1e-6 cull, a hit mask -- flips within that rounding; the median and the "
                              "99.9th percentile show the arithmetic (tests/test_precision_gpu.py anchors the modes on a float64 evaluation)")
-    if world == 1 and not args.no_legs and args.vis == "mlp":
+    if args.full and world == 1 and not args.no_legs and args.vis == "mlp":
         # The other synthetic scene at the headline precision (2 steps): hit fraction, visibility pairs per hit ray and rate
         other = "nonconvex" if args.scene == "sphere" else "sphere"
         with contextlib.redirect_stdout(sys.stderr):
@@ -668,7 +704,7 @@ def main():
                                "visibility_pairs_per_hit_ray": int(st2["diffuse_vis_evals"]) / 2 / max(hits2, 1.0),
                                "this_scene_pairs_per_hit_ray": evals / max(args.steps, 1) / max(hit_frac * H * W, 1.0)}
         del model2
-    if world == 1 and not args.no_configs and args.vis == "mlp":
+    if args.full and world == 1 and not args.no_configs and args.vis == "mlp":
         # The other BASELINE configurations, outside the timed region, at the headline precision (--with-split: in split precision too)
         bench_configs.install_timers()
         cfgs = {}
@@ -689,7 +725,7 @@ def main():
         line["configs_note"] = ("BASELINE.json configs 1, 2, 3, 5 (tools/bench_configs.py), best of 2 repetitions after a warm-up "
                                 "(config 5: one pass over a band of chunks; `--config 5` times all 1875), single GPU, each with "
                                 "the roofline of the op that dominates it from HIP events around that op")
-    if world == 1 and not args.no_configs and args.vis == "mlp":
+    if args.full and world == 1 and not args.no_configs and args.vis == "mlp":
         # Three figures that used to be builder-only, outside the timed region, default settings:
         # (1) the whole BASELINE config 5 view, all 1875 chunks chunk by chunk (the `configs` entry above is a band of them)
         extras = {}
@@ -715,7 +751,7 @@ def main():
         extras["runner_plot_loop"] = runner_loop_replay(model, uv_d, pose_d, K_d, hdr)
         line["extras"] = extras
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(model, args.cpu_baseline_chunks, uv, pose, K)
             # the reference's runners pin torch to one thread (training/train_pbr.py:24): that figure too, on a smaller sample
             one = cpu_baseline(model, 1, uv, pose, K, cores=1, pixels=args.cpu_baseline_1thread_pixels)

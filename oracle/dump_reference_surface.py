@@ -1,8 +1,8 @@
 """Dump the PUBLIC SURFACE of the nine reference modules the overlay shadows as JSON: for every public
 function / class defined in the module, its parameters (name, kind, repr of the default) and, for classes, the same for every public
 method plus __init__ / __call__, and the base-class names.  TEST INFRASTRUCTURE (build container only): an interface description --
-names and parameter lists, no source text -- committed as tests/golden/reference_surface.json and checked by tests/test_surface_cpu.py,
-which re-runs this dump when /root/reference is present and asserts the committed file is current.
+names and parameter lists, no source text -- committed as tests/golden/reference_surface.json, against which tests/test_surface_cpu.py
+checks the overlay; re-run this dump by hand against a reference checkout (oracle/ref_shim.py) to refresh the committed file.
 
     python oracle/dump_reference_surface.py [out.json]
 """

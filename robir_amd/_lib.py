@@ -32,7 +32,8 @@ ABI_VERSION = 8
 def build(verbose=False, legacy=True):
     """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library) and -- legacy=True --
     librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
-    jobs = str(min(8, os.cpu_count() or 1))
+    # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
+    jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j", jobs, "all" if legacy else "default"],
                        capture_output=not verbose, text=True)
     if r.returncode != 0:

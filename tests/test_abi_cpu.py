@@ -23,7 +23,7 @@ def _exported(path):
 def test_library_exports_header_symbols():
     """The default library exports exactly what include/robir_hip.h declares (ABI version 8: 89 entry points -- the retired kernel
     generations left it in round 5, the seven helper kernels of csrc/surface.hip and rb_cesr_net_f16_points joined in round 6), the legacy library -- where it has
-    been built: ROBIR_BUILD_LEGACY=1, optional since round 6 -- exactly that plus include/robir_hip_legacy.h."""
+    been built: build()'s default, skipped under ROBIR_BUILD_LEGACY=0 -- exactly that plus include/robir_hip_legacy.h."""
     from robir_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build(legacy=False)
@@ -182,26 +182,30 @@ def test_overlay_exports_reference_names():
             del sys.modules[k]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model"), reason="needs the reference checkout (build container only)")
-def test_overlay_shadows_reference_modules_by_path_order():
+def test_overlay_shadows_reference_modules_by_path_order(tmp_path):
     """INTEGRATION.md seam B: with overlay/ ahead of the reference on the path, `model.<overlaid>` comes from this repo and
     every other `model.*` module still comes from the reference (PEP-420: `model/` has no __init__.py on either side).
+    The reference checkout is stood in for by a tree of the same layout (`model/` without __init__.py, one file per module name).
     Run in a subprocess so that the module cache of the test session stays clean."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ref = tmp_path / "reference"
+    (ref / "model").mkdir(parents=True)
+    for name in ("sg_render", "octree_tracing", "loss"):
+        (ref / "model" / f"{name}.py").write_text("")
     code = (
         "import sys, importlib.util\n"
         "a = importlib.util.find_spec('model.sg_render').origin\n"
         "b = importlib.util.find_spec('model.octree_tracing').origin\n"
         "c = importlib.util.find_spec('model.loss').origin\n"
         "print(a); print(b); print(c)\n")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(root, "overlay"), root, "/root/reference"]))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(root, "overlay"), root, str(ref)]))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
     assert out.returncode == 0, out.stderr
     a, b, c = out.stdout.strip().splitlines()[-3:]
     assert a.startswith(os.path.join(root, "overlay")) and b.startswith(os.path.join(root, "overlay"))
-    assert c.startswith("/root/reference/model")
+    assert c.startswith(str(ref / "model"))
 
 
 def test_forward_only_guard():

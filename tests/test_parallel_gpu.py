@@ -107,14 +107,15 @@ def test_two_ranks_render_one_view_bit_identically(hw):
 
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` from the plain driver command (no launcher, WORLD_SIZE unset): bench.py starts the two ranks
-    itself; on this one-GPU box they share cuda:0 over gloo, on a node the same entry uses RCCL.  One JSON line, two ranks."""
+    itself; on this one-GPU box they share cuda:0 over gloo, on a node the same entry uses RCCL.  One JSON line, two ranks
+    (`--full`: with the weak-scaling views and the collective timed alone)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--precision", "split"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--precision", "split", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]

@@ -2,13 +2,12 @@
 constant of the nine reference modules it shadows, with the reference's parameter order and defaults.
 
 tests/golden/reference_surface.json is the reference's surface as dumped by oracle/dump_reference_surface.py (names and parameter lists:
-an interface description).  Where /root/reference is present (the build container) the dump is re-run and must equal the committed file.
+an interface description); re-run that script by hand against a reference checkout to refresh it.
 OUT-OF-SCOPE names (the allow-list below, each with its SURVEY.md section-2 reason) must be PRESENT and raise NotImplementedError."""
 import importlib
 import inspect
 import json
 import os
-import subprocess
 import sys
 
 import pytest
@@ -168,12 +167,3 @@ def test_only_listed_names_raise_not_implemented(overlay_modules):
     # the protocol classes of model/sdf_render.py:10-34 raise NotImplementedError in the reference too
     stubs = [s for s in stubs if not s.startswith(("sdf_render.IComp.", "sdf_render.ISDF."))]
     assert not stubs, stubs
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model"), reason="needs the reference checkout (build container only)")
-def test_committed_surface_is_current(tmp_path):
-    out = tmp_path / "surface.json"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "dump_reference_surface.py"), str(out)], capture_output=True, text=True,
-                       cwd=ROOT, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert json.load(open(out)) == json.load(open(SURFACE)), "re-run `python oracle/dump_reference_surface.py` and commit the result"

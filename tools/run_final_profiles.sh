@@ -19,11 +19,11 @@ pmc() {   # name, grep pattern, command... (two SQ passes + FETCH_SIZE + WRITE_S
     python tools/rocpd_summary.py $(find $O/p -name "*.db" | head -1) | grep -i "$pat" >> $O/${TAG}_${name}_pmc.md; rm -rf $O/p
   done
 }
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/bench.err
 python bench.py --precision split --steps 5 --warmup 2 --no-legs --no-configs --no-cpu-baseline > $O/${TAG}_bench_split.json 2>> $O/bench.err
 python bench.py --vis octree --steps 3 --no-legs --no-configs --no-cpu-baseline > $O/${TAG}_bench_octree_vis.json 2>> $O/bench.err
 python bench.py --scene nonconvex --steps 3 --no-legs --no-configs --no-cpu-baseline > $O/${TAG}_bench_nonconvex.json 2>> $O/bench.err
-python bench.py --gpus 8 --steps 1 --warmup 1 > $O/${TAG}_bench_8rank_shared_gpu.json 2>> $O/bench.err
+python bench.py --full --gpus 8 --steps 1 --warmup 1 > $O/${TAG}_bench_8rank_shared_gpu.json 2>> $O/bench.err
 for C in 2 3 5; do python bench.py --config $C --precision split --steps 2 > $O/${TAG}_config${C}_split.json 2>> $O/bench.err; done
 prof bench python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-legs --no-configs
 prof bench_split python bench.py --precision split --steps 2 --warmup 1 --no-cpu-baseline --no-legs --no-configs

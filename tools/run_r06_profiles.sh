@@ -19,11 +19,11 @@ pmc() {   # name, grep pattern, command... (two SQ passes + FETCH_SIZE + WRITE_S
     python tools/rocpd_summary.py $(find $O/p -name "*.db" | head -1) | grep -i "$pat" >> $O/${TAG}_${name}_pmc.md; rm -rf $O/p
   done
 }
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/bench.err
 python bench.py --vis octree --steps 3 --no-legs --no-configs --no-cpu-baseline > $O/${TAG}_bench_octree_vis.json 2>> $O/bench.err
 python bench.py --scene nonconvex --steps 3 --no-legs --no-configs --no-cpu-baseline > $O/${TAG}_bench_nonconvex.json 2>> $O/bench.err
-python bench.py --gpus 8 --steps 1 --warmup 1 > $O/${TAG}_bench_8rank_shared_gpu.json 2>> $O/bench.err
-python bench.py --precision f16 --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_f16.json 2>> $O/bench.err
+python bench.py --full --gpus 8 --steps 1 --warmup 1 > $O/${TAG}_bench_8rank_shared_gpu.json 2>> $O/bench.err
+python bench.py --full --precision f16 --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_f16.json 2>> $O/bench.err
 python bench.py --config 5 --precision f16 --steps 3 > $O/${TAG}_config5_f16.json 2>> $O/bench.err
 python bench.py --config 5 --steps 2 > $O/${TAG}_config5_exact.json 2>> $O/bench.err
 prof bench python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-legs --no-configs
