@@ -9,7 +9,8 @@
 // fragments of 1 KB, streamed through a 4-slot LDS ring by LDS-DMA three chunks ahead under counted waits (K / 128 copies per wave and
 // chunk: a third of the exact-operand stream's bytes for a sixth of its MFMAs -- the copies' issue cost is what bounds this kernel, so
 // T = 3 tiles amortise them over 48 MFMAs); per k-block ONE fragment read feeds T MFMAs; the previous chunk's epilogue (softplus + pack,
-// seven single-instruction steps per value) goes two steps behind every MFMA (x6t_engine.h: the k-major finding of round 6).
+// seven single-instruction steps per value) goes two steps behind every MFMA (tools/microbench/mfma_order.hip: two vector instructions
+// behind every MFMA cost 17.9 cycles per MFMA, eight behind every fourth 23.8).
 // All biases are resident in the LDS; the encoded rows of a round too (the skip layer's input part is rebuilt from them).
 #include "../../include/robir_hip.h"
 #include "common.h"
@@ -18,12 +19,9 @@
 #include "x6t_engine.h"
 #include <type_traits>
 
-#ifndef FX_CG
-#define FX_CG 1             // MFMAs between two LDS-DMA copies of a wave within a chunk (4: measured no gain, 3.47 / 3.40 -> 3.59 / 3.42 ms: profiles/r06_dma_placement.md)
-#endif
-
 namespace rb {
 
+constexpr int FX_NTILES = 3;              // 16-row tiles per wave (T = 2 measured worse and was removed: DESIGN section 9(a))
 constexpr int FX_SLOT_B = 18 * 1024;      // K = 576: eighteen 1 KB fragments
 template <int K0P, int N3P>
 struct FxNet {
@@ -284,15 +282,13 @@ __global__ __launch_bounds__(256, 1) void k_cesr_f16(const float* __restrict__ X
             if (j2 < NCH) win[(sl - 1) % D] = frag_of(ring_lane + slot_b[j2 & 3], k2);
           }
           if (s == NSLOT - T) nbias = bias_of(cb + jb + 1);
-          // copy i of this wave goes behind MFMA FX_CG i
-          // (a short chunk -- layer 0's K = 64 / 192 -- packs them closer: all of them must fit its NSLOT positions)
-          const int cg_fit = NC3 > 1 ? (NSLOT - 1) / (NC3 - 1) : 1;
-          const int cg = cg_fit < 1 ? 1 : (cg_fit < FX_CG ? cg_fit : FX_CG);
-          const bool copy_here = s % cg == 0 && s / cg < NC3;
-          const int copies_before = (s + cg - 1) / cg < NC3 ? (s + cg - 1) / cg : NC3;
+          // copy i of this wave goes behind MFMA i (one every four MFMAs measured no better, 3.47 / 3.40 -> 3.59 / 3.42 ms, and was
+          // removed: profiles/r06_dma_placement.md)
+          const bool copy_here = s < NC3;
+          const int copies_before = s < NC3 ? s : NC3;
           if (copy_here) {
 #ifndef FX_ABL_NODMA                     // timing ablation (wrong results): no LDS-DMA copies after the prologue's
-            xt_copy_piece_seq(s / cg, src3, dst3, lv);
+            xt_copy_piece_seq(s, src3, dst3, lv);
 #endif
           } else if (nep > 0) {
             const int m0 = PER * (s - copies_before);
@@ -378,10 +374,7 @@ extern "C" int rb_cesr_net_f16_points(const float* x, long M, int kind, int n_la
                                       rb_stream_t stream) {
   if (M <= 0) return 0;
   RB_REQUIRE(x && Wp && Y, "null pointer");
-#ifndef FX_TILES
-#define FX_TILES 3          // tiles per wave the library is built with (2 or 3: one instance per net keeps the build short)
-#endif
-  RB_REQUIRE(tiles == FX_TILES, "this build carries one tile count (FX_TILES)");
+  RB_REQUIRE(tiles == FX_NTILES, "the library carries one tile count per wave: 3");
   const int pg = persistent_grid((M + 64 * tiles - 1) / (64 * tiles), n_workgroups);
   if (pg <= 0) return rb::fail(__func__, "device query failed");
   const unsigned grid = (unsigned)pg;
@@ -389,10 +382,10 @@ extern "C" int rb_cesr_net_f16_points(const float* x, long M, int kind, int n_la
   hipStream_t s = (hipStream_t)stream;
   const f4* W = (const f4*)Wp;
   switch (kind) {
-    case 0: hipLaunchKernelGGL((k_cesr_f16<64, 464, false, FX_TILES>), dim3(grid), dim3(256), 0, s, x, M, 1, W, 3, Y, rw); break;
+    case 0: hipLaunchKernelGGL((k_cesr_f16<64, 464, false, FX_NTILES>), dim3(grid), dim3(256), 0, s, x, M, 1, W, 3, Y, rw); break;
     case 2:
       RB_REQUIRE(n_label >= 1 && n_label <= 128, "n_label must be 1..128");
-      hipLaunchKernelGGL((k_cesr_f16<192, 336, true, FX_TILES>), dim3(grid), dim3(256), 0, s, x, M, n_label, W, 2, Y, rw);
+      hipLaunchKernelGGL((k_cesr_f16<192, 336, true, FX_NTILES>), dim3(grid), dim3(256), 0, s, x, M, n_label, W, 2, Y, rw);
       break;
     default: return rb::fail(__func__, "kind: 0 normal_net on PE10(x), 2 shadow_net on (point, one-hot label) rows");
   }

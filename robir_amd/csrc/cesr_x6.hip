@@ -5,24 +5,14 @@
 // its two halves) with the softplus epilogue of sdf_x6.hip; the skip layer's input part [x0 | 0] / sqrt 2 is rebuilt at that layer from
 // the encoder's LDS rows and the label (operands + next operands already take 408 of the 512 registers: nothing else stays resident).
 // Replaces k_softplus512 (f32-input MFMA: 41 % of BASELINE config 5 at the default precision).  Weights: packing.pack_softplus512_x6.
+// The products h.xl and l.xh of the K = 256 layers as bf8 MFMAs (as in vis_diffuse_x6t.hip) measured slower, with 267 / 321 spilled
+// registers, and were removed (profiles/r06_fp8_c2.md).
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include "x6_ring.h"
 #include "x6t_engine.h"
 #include <type_traits>
-
-#ifndef QX_FP8
-#define QX_FP8 0            // 1 (needs QX_FINE): EXPERIMENT -- in the layers whose units are K = 256 the products h.xl and l.xh as bf8 MFMAs (vis_diffuse_x6t.hip XT_FP8)
-#endif
-#ifndef QX_FINE
-#define QX_FINE 1           // a filler slot behind EVERY MFMA, the previous chunk's softplus + split as single-instruction steps (0: two clusters per chunk; -1.3 % / -2 %, bit-identical: profiles/r06_dma_placement.md)
-#endif
-#ifndef QX_SPREAD
-#define QX_SPREAD 1         // the LDS-DMA copies of a unit one at a time, three MFMAs apart (0: blocks of 1 / 4 / 2 instructions; profiles/r06_dma_placement.md: -2.4 %)
-#endif
-
-static_assert(!QX_FP8 || QX_FINE, "QX_FP8 is written into the QX_FINE form of the k-block");
 
 namespace rb {
 
@@ -91,10 +81,6 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
   unsigned sat = 0u;
   u4 xh[18], xm[18], xl[18];           // operands of the current layer (K <= 576): three pieces, one tile
   u4 yh[16], ym[16], yl[16];           // ... of the next layer
-#if QX_FP8
-  typedef int qx_i8 __attribute__((ext_vector_type(8)));
-  qx_i8 xh8[4], xl8[4], yh8[4], yl8[4];      // bf8 copies of the h and l pieces for the layers that run two products on the bf8 MFMA (K = 512: four groups of 128)
-#endif
   long rrow = 0;
   int label = -1;
 
@@ -187,14 +173,11 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
     constexpr int LI = decltype(LI_tag)::value;
     constexpr int KU = Net::kunit(LI), KB = KU / 32, HV = Net::hv(LI), NU = Net::nunits(LI), UB = Net::ubase(LI);
     constexpr bool OUT = LI == 8, SKIPOUT = LI == 3;
-    constexpr bool FP8 = QX_FP8 && KU == 256;                       // this layer's weights are in the bf8 layout (packing.repack_x6_chunks_fp8)
-    constexpr bool NEXT_FP8 = QX_FP8 && LI != 3 && LI != 8;         // ... and so are the next layer's: its operands get bf8 copies instead of f16 l pieces
-#ifndef QX_DB
-#define QX_DB 1              // fragment sets read ahead per k-block: 2 measured 1 % slower (and 66 instead of 42 spilled registers in the shadow_net instance)
-#endif
-    constexpr int BS = 1, DB = KB >= 6 ? QX_DB : 1, D = BS * DB, NB = BS * (DB + 1);      // three fragment sets: the register file is full
+    // the fragments of ONE k-block read ahead (two measured 1 % slower, with 66 instead of 42 spilled registers in the shadow_net
+    // instance, and were removed): the register file is full
+    constexpr int D = 1, NB = D + 1;
     constexpr int HB = KB / 2, NSTEP = NU * KB;
-    static_assert(D + BS - 1 <= KB - HB, "reads of the next unit start after the barrier");
+    static_assert(D <= KB - HB, "reads of the next unit start after the barrier");
     SxAcc accs[2];
     f4 bnext = f4{0.f, 0.f, 0.f, 0.f};
     u4 wfh[NB], wfm[NB], wfl[NB];
@@ -230,12 +213,12 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
         hidden_pair(a, pj, q);
       }
     };
-#if QX_FINE
     // The epilogue of a hidden chunk (four values per lane) as single-instruction steps in a skewed order: step 4 t + r = stage t - r of
     // value r (stages: two combines, -|z| k, exp2, 1 + e, log2, max, fma [, / sqrt 2]) -- consecutive steps belong to different values, a
     // step's input is four steps old, at most every other step is a quarter-rate transcendental -- then the two pairs' exact three-way
     // splits (sx_split_pair's instructions, the pairs alternating) and the sentinel.  The same operations in the same order per value as
-    // hidden_pair(): bit-identical results.
+    // hidden_pair(): bit-identical results.  (Two clusters per chunk instead of a step behind every MFMA measured 1.3 % / 2.0 % slower
+    // and were removed: profiles/r06_dma_placement.md.)
     constexpr int FNS = SKIPOUT ? 9 : 8, FNA = 4 * (FNS + 3), FNP = 2 * 11, FNSTEP = FNA + FNP;
     float f_t[4], f_z[4], f_e[4], f_u[4], f_v[4];
     unsigned f_h[2], f_m[2], f_l[2];
@@ -270,41 +253,20 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
           const int o = (pj & 1) * 2 + q;
           yh[pj >> 1][o] = f_h[q];
           ym[pj >> 1][o] = f_m[q];
-#if QX_FP8
-          if constexpr (NEXT_FP8) {
-            if (q == 1) {      // the top bytes of the block's four h / l halves: dword pj of the next layer's bf8 operands
-              yh8[pj >> 3][pj & 7] = (int)__builtin_amdgcn_perm(f_h[1], f_h[0], 0x07050301u);
-              yl8[pj >> 3][pj & 7] = (int)__builtin_amdgcn_perm(f_l[1], f_l[0], 0x07050301u);
-            }
-          } else
-#endif
           yl[pj >> 1][o] = f_l[q];
           sat = sat_acc_pos(sat, f_h[q]);
         }
       }
     };
-#endif
     zero_acc(accs[0], bias_of(0));
 #pragma unroll
     for (int i = 0; i < D; ++i)
       if (i < NSTEP) {
-#if QX_FP8
-        if constexpr (FP8) {      // a group of 128 K = 768 lane-strided u4: [k-block 0..3][h | m] (512), h8 (128), l8 (128)
-          const u4* f = frag_of(i / KB) + ((i % KB) >> 2) * 768 + (2 * ((i % KB) & 3)) * 64;
-          wfh[i % NB] = f[0];
-          wfm[i % NB] = f[64];
-        } else
-#endif
-        {
-          const u4* f = frag_of(i / KB) + (3 * (i % KB)) * 64;
-          wfh[i % NB] = f[0];
-          wfm[i % NB] = f[64];
-          wfl[i % NB] = f[128];
-        }
+        const u4* f = frag_of(i / KB) + (3 * (i % KB)) * 64;
+        wfh[i % NB] = f[0];
+        wfm[i % NB] = f[64];
+        wfl[i % NB] = f[128];
       }
-#if QX_FP8
-    qx_i8 w8h, w8l;
-#endif
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       const int c = u / HV, hvi = u % HV;
@@ -314,16 +276,14 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
       (void)dummy2;
       const int L3 = u + 3 < NU ? LI : Net::layer_of(UB + u + 3);
       const int K3 = Net::kunit(L3);
-      const int nu3 = sx_units(K3);
-      (void)nu3;
       const long in_layer = (long)((u + 3) / HV) * Net::chunk_f4s(LI) + (long)((u + 3) % HV) * (KU / 32) * 192;
       const f4* src3 = u + 3 < NU ? wl + in_layer : wnext[u + 3 - NU < 3 ? u + 3 - NU : 0];
       const int sl3 = (u + 3) & 3;
       const unsigned dst3 = ring_b + slot_b[sl3], bdst3 = bias_b + bslot_b[sl3];
-#if QX_SPREAD
       // The copies of unit u+3 ONE AT A TIME behind every third MFMA of the unit's second half instead of blocks of 1 / 4 / 2
-      // (tools/ubench/dma_stagger.hip: back-to-back copies cost the issuing wave ~70 cycles each, copies four MFMAs apart ~26): copy 0 = the
-      // bias head, copy c = piece c - 1 of this wave's span (M0 carried from piece to piece as in x6t_engine.h: nothing else writes it).
+      // (tools/ubench/dma_stagger.hip: back-to-back copies cost the issuing wave ~70 cycles each, copies four MFMAs apart ~26; the blocks
+      // measured 2.4 % slower and were removed: profiles/r06_dma_placement.md): copy 0 = the bias head, copy c = piece c - 1 of this
+      // wave's span (M0 carried from piece to piece as in x6t_engine.h: nothing else writes it).
       const int ncp3 = sx_np(K3), ns3 = sx_ns(K3), nsw3 = sx_nsw(K3);
       const int first3 = wave * nsw3 < ns3 - nsw3 ? wave * nsw3 : ns3 - nsw3;
       const f4* span3 = src3 + 4 + first3 * 64;
@@ -341,7 +301,6 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
             else xt_copy_piece_seq(cidx - 1, span3, dspan3, lv3, true);
           }
       };
-#endif
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
         const int st = u * KB + kb;
@@ -363,75 +322,15 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
 #else
           if (s2 < NSTEP) {
 #endif
-#if QX_FP8
-            if constexpr (FP8) {
-              const u4* f = frag_of(s2 / KB) + ((s2 % KB) >> 2) * 768 + (2 * ((s2 % KB) & 3)) * 64;
-              wfm[s2 % NB] = f[64];
-              wfh[s2 % NB] = f[0];
-            } else
-#endif
-            {
-              const u4* f = frag_of(s2 / KB) + (3 * (s2 % KB)) * 64;
-              wfl[s2 % NB] = f[128];
-              wfm[s2 % NB] = f[64];
-              wfh[s2 % NB] = f[0];
-            }
+            const u4* f = frag_of(s2 / KB) + (3 * (s2 % KB)) * 64;
+            wfl[s2 % NB] = f[128];
+            wfm[s2 % NB] = f[64];
+            wfh[s2 % NB] = f[0];
           }
         }
-#if QX_FP8
-        if constexpr (FP8) {
-          if ((kb & 3) == 0) {      // the group's two bf8 fragments: four reads, used behind the group's last k-block
-            const u4* f8 = frag_of(u) + (kb >> 2) * 768 + 512;
-            const u4 a0 = f8[0], a1 = f8[64], b0 = f8[128], b1 = f8[192];
-            w8h = qx_i8{(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
-            w8l = qx_i8{(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], (int)b1[2], (int)b1[3]};
-          }
-        }
-#endif
         {
           const int xk = hvi * KB + kb;
 #define QX_MFMA(ACC, W, X) ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, W), __builtin_bit_cast(h8, X), ACC, 0, 0, 0)
-#if QX_FINE && QX_FP8
-          if constexpr (FP8) {
-            // four f16 products per k-block + two bf8 MFMAs per group of four: 4 KB + 2 (KB / 4) slots per unit
-            constexpr int NSC8 = HV * (KB * 4 + (KB / 4) * 2);
-            constexpr int FPER8_ = (FNSTEP + NSC8 - 1) / NSC8, FPER8 = FPER8_ > 4 ? 4 : FPER8_;
-            const bool fine_here8 = !OUT && c > 0;
-            const int sbase8 = hvi * (KB * 4 + (KB / 4) * 2) + kb * 4 + (kb >> 2) * 2;
-#define QX_SLOT8(J)                                                                                    \
-  {                                                                                                    \
-    if (fine_here8) {                                                                                  \
-      const int sc_ = sbase8 + (J);                                                                    \
-      _Pragma("unroll") for (int i_ = 0; i_ < FPER8; ++i_)                                             \
-        if (FPER8 * sc_ + i_ < FNSTEP) fine_step(FPER8 * sc_ + i_, c - 1, accs[(c - 1) & 1]);          \
-    }                                                                                                  \
-    if (QX_SPREAD && kb >= HB && ((J) == 1 || (J) == 3)) spread_site(2 * (kb - HB) + ((J) == 3));      \
-    __builtin_amdgcn_sched_barrier(0);                                                                 \
-  }
-            QX_MFMA(acc.c2, wfm[st % NB], xm[xk]);
-            QX_SLOT8(0)
-            QX_MFMA(acc.c1, wfm[st % NB], xh[xk]);
-            QX_SLOT8(1)
-            QX_MFMA(acc.c1, wfh[st % NB], xm[xk]);
-            QX_SLOT8(2)
-            QX_MFMA(acc.c0, wfh[st % NB], xh[xk]);
-            QX_SLOT8(3)
-            if ((kb & 3) == 3) {
-              acc.c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w8l, xh8[xk >> 2], acc.c2, 1, 1, 0, 0, 0, 0);
-              QX_SLOT8(4)
-              acc.c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w8h, xl8[xk >> 2], acc.c2, 1, 1, 0, 0, 0, 0);
-              QX_SLOT8(5)
-            }
-#undef QX_SLOT8
-            if (fine_here8 && hvi == HV - 1 && kb == KB - 1) {
-#pragma unroll
-              for (int m_ = 0; m_ < FNSTEP; ++m_)
-                if (m_ >= FPER8 * NSC8) fine_step(m_, c - 1, accs[(c - 1) & 1]);
-            }
-          } else
-#endif
-#if QX_FINE
-          {
           // a filler slot behind EVERY MFMA: the steps of chunk c-1's epilogue (hidden layers), the copies at their two sites per k-block
           constexpr int NSC = HV * KB * 6;                                        // MFMAs (= slots) per chunk
           constexpr int FPER_ = (FNSTEP + NSC - 1) / NSC, FPER = FPER_ > 4 ? 4 : FPER_;
@@ -443,7 +342,7 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
       _Pragma("unroll") for (int i_ = 0; i_ < FPER; ++i_)                                            \
         if (FPER * sc_ + i_ < FNSTEP) fine_step(FPER * sc_ + i_, c - 1, accs[(c - 1) & 1]);          \
     }                                                                                                \
-    if (QX_SPREAD && kb >= HB && ((J) == 2 || (J) == 5)) spread_site(2 * (kb - HB) + ((J) == 5));   \
+    if (kb >= HB && ((J) == 2 || (J) == 5)) spread_site(2 * (kb - HB) + ((J) == 5));                 \
     if ((J) < 5) __builtin_amdgcn_sched_barrier(0);                                                  \
   }
           QX_MFMA(acc.c2, wfl[st % NB], xh[xk]);
@@ -464,44 +363,12 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
             for (int m_ = 0; m_ < FNSTEP; ++m_)
               if (m_ >= FPER * NSC) fine_step(m_, c - 1, accs[(c - 1) & 1]);
           }
-          }
-#else
-          QX_MFMA(acc.c2, wfl[st % NB], xh[xk]);
-          QX_MFMA(acc.c2, wfm[st % NB], xm[xk]);
-          QX_MFMA(acc.c2, wfh[st % NB], xl[xk]);
-#if QX_SPREAD
-          if (kb >= HB) {
-            spread_site(2 * (kb - HB));
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#endif
-          QX_MFMA(acc.c1, wfm[st % NB], xh[xk]);
-          QX_MFMA(acc.c1, wfh[st % NB], xm[xk]);
-          QX_MFMA(acc.c0, wfh[st % NB], xh[xk]);
-#endif
 #undef QX_MFMA
         }
 #ifndef QX_ABL_NOEPI                     // timing ablation (wrong results): no softplus / split between the MFMAs
-        if (c > 0 && hvi == 0 && (OUT || !QX_FINE)) {              // softplus + three-way split (or the store) of chunk c-1
+        if (c > 0 && hvi == 0 && OUT) {                             // the store of chunk c-1
           if (kb == 0) epilogue(accs[(c - 1) & 1], c - 1, 0);
           if (kb == (KB >= 6 ? 3 : 1)) epilogue(accs[(c - 1) & 1], c - 1, 1);
-        }
-#endif
-#if QX_SPREAD
-        if (kb >= HB && !QX_FINE) spread_site(2 * (kb - HB) + 1);
-#else
-        if (kb >= HB) {
-#pragma unroll
-          for (int un = 0; un < 3; ++un)
-            if (un < nu3 && (un * (KB - HB)) / nu3 == kb - HB) {
-#ifdef QX_ABL_NODMA                      // timing ablation (wrong results): no LDS-DMA copies after the prologue's
-              continue;
-#endif
-              if (K3 == 64) qx_copy<64>(un, src3, lane4, lane16, bdst3, dst3, wave);
-              else if (K3 == 192) qx_copy<192>(un, src3, lane4, lane16, bdst3, dst3, wave);
-              else if (K3 == 256) qx_copy<256>(un, src3, lane4, lane16, bdst3, dst3, wave);
-              else qx_copy<288>(un, src3, lane4, lane16, bdst3, dst3, wave);
-            }
         }
 #endif
         __builtin_amdgcn_sched_barrier(0);
@@ -523,16 +390,8 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
     }
     constexpr int NCH = NU / HV;
     const SxAcc& last = accs[(NCH - 1) & 1];
-#if QX_FINE && QX_FP8
-    if constexpr (!OUT) {      // the last chunk through the same steps (they also fill the bf8 operands)
-#pragma unroll
-      for (int m_ = 0; m_ < FNSTEP; ++m_) fine_step(m_, NCH - 1, last);
-    } else
-#endif
-    {
-      epilogue(last, NCH - 1, 0);
-      epilogue(last, NCH - 1, 1);
-    }
+    epilogue(last, NCH - 1, 0);
+    epilogue(last, NCH - 1, 1);
     if constexpr (SKIPOUT) {
       build_skip_operands();
       fold_sat_in();
@@ -541,17 +400,8 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
       for (int kb = 0; kb < 16; ++kb) {
         xh[kb] = yh[kb];
         xm[kb] = ym[kb];
-        if constexpr (!NEXT_FP8) xl[kb] = yl[kb];
+        xl[kb] = yl[kb];
       }
-#if QX_FP8
-      if constexpr (NEXT_FP8) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          xh8[gq] = yh8[gq];
-          xl8[gq] = yl8[gq];
-        }
-      }
-#endif
     }
   };
 

@@ -23,11 +23,10 @@ namespace rb {
 
 constexpr int BX_SLOT_B = 24 * 1024 + 512;
 constexpr int BX_NCHUNK = 117;
-#ifndef BX_NSLOT
-#define BX_NSLOT 4                       // ring slots: copies run BX_NSLOT - 1 chunks ahead of the MFMAs (5: measured the same, 13.0-13.3 vs
-                                         // 13.0-13.5 ms per 2^20 points for value + gradient: the copies' latency is not what the waves wait for)
-#endif
-constexpr int BX_AH = BX_NSLOT - 1;
+constexpr int BX_SLOTS = 4;              // ring slots: copies run BX_SLOTS - 1 chunks ahead of the MFMAs (5 measured the same, 13.0-13.3 vs
+                                         // 13.0-13.5 ms per 2^20 points for value + gradient, and was removed: the copies' latency is not
+                                         // what the waves wait for)
+constexpr int BX_AH = BX_SLOTS - 1;
 __host__ __device__ constexpr int bx_K(int l) { return l == 4 ? 224 : 256; }
 __host__ __device__ constexpr int bx_nch(int l) { return l == 3 ? 17 : (l == 7 ? 4 : 16); }
 __host__ __device__ constexpr int bx_cbase(int l) {
@@ -63,8 +62,8 @@ static_assert(sx_np(224) == 7 && sx_np(256) == 7 && sx_units(224) == 3 && sx_uni
 __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ sig, long M, const f4* __restrict__ Wt,
                                                          const float* __restrict__ w8row, float* __restrict__ gfeat,
                                                          unsigned* __restrict__ range_word) {
-  __shared__ f4 ring[BX_NSLOT * BX_SLOT_B / 16];       // 98 / 123 KB
-  __shared__ f4 bias_ring[BX_NSLOT * 16];
+  __shared__ f4 ring[BX_SLOTS * BX_SLOT_B / 16];       // 98 KB
+  __shared__ f4 bias_ring[BX_SLOTS * 16];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long nrounds = (M + 63) >> 6;
@@ -75,9 +74,9 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ s
   const unsigned ring_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)ring);
   const unsigned bias_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)bias_ring);
   const unsigned lane16 = (unsigned)lane * 16u, lane4 = (unsigned)lane * 4u;
-  unsigned slot_b[BX_NSLOT], bslot_b[BX_NSLOT];
+  unsigned slot_b[BX_SLOTS], bslot_b[BX_SLOTS];
 #pragma unroll
-  for (int i = 0; i < BX_NSLOT; ++i) {
+  for (int i = 0; i < BX_SLOTS; ++i) {
     slot_b[i] = (unsigned)i * BX_SLOT_B;
     bslot_b[i] = (unsigned)i * 256u;
   }
@@ -131,8 +130,8 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ s
 #pragma unroll
     for (int i = 0; i < BX_AH; ++i) wnext[i] = Wt + bx_coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
-    auto frag_of = [&](int c) { return reinterpret_cast<const u4*>(reinterpret_cast<const char*>(ring) + slot_b[c % BX_NSLOT]) + lane; };
-    auto bias_of = [&](int c) { return *(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(bias_ring) + bslot_b[c % BX_NSLOT]) + g); };
+    auto frag_of = [&](int c) { return reinterpret_cast<const u4*>(reinterpret_cast<const char*>(ring) + slot_b[c % BX_SLOTS]) + lane; };
+    auto bias_of = [&](int c) { return *(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(bias_ring) + bslot_b[c % BX_SLOTS]) + g); };
     auto zero_acc = [&](SxAcc& a, const f4& b) {
       a.c0 = b;
       a.c1 = f4{0.f, 0.f, 0.f, 0.f};
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ s
       (void)dummy2;
       const int K3 = jb + BX_AH < NCH ? K : bx_K(bx_layer_of(CB + jb + BX_AH));
       const f4* src3 = jb + BX_AH < NCH ? wl + (long)(jb + BX_AH) * sx_cf4(K) : wnext[jb + BX_AH - NCH < BX_AH ? jb + BX_AH - NCH : 0];
-      const int sl3 = (jb + BX_AH) % BX_NSLOT;
+      const int sl3 = (jb + BX_AH) % BX_SLOTS;
       const unsigned dst3 = ring_b + slot_b[sl3], bdst3 = bias_b + bslot_b[sl3];
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
@@ -249,15 +248,15 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ s
       }
     }
     {   // slot 0 = the slot of the next layer's first chunk
-      constexpr int R = NCH % BX_NSLOT;
-      unsigned a[BX_NSLOT], b[BX_NSLOT];
+      constexpr int R = NCH % BX_SLOTS;
+      unsigned a[BX_SLOTS], b[BX_SLOTS];
 #pragma unroll
-      for (int i = 0; i < BX_NSLOT; ++i) {
-        a[i] = slot_b[(i + R) % BX_NSLOT];
-        b[i] = bslot_b[(i + R) % BX_NSLOT];
+      for (int i = 0; i < BX_SLOTS; ++i) {
+        a[i] = slot_b[(i + R) % BX_SLOTS];
+        b[i] = bslot_b[(i + R) % BX_SLOTS];
       }
 #pragma unroll
-      for (int i = 0; i < BX_NSLOT; ++i) {
+      for (int i = 0; i < BX_SLOTS; ++i) {
         slot_b[i] = a[i];
         bslot_b[i] = b[i];
       }

@@ -20,10 +20,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef SX_PK
-#define SX_PK 0      // 1: the softplus stage on value pairs (v_pk_* f32): bit-identical, measured 1 % slower (profiles/r03_sdf_x6_ablation.md)
-#endif
-
 namespace rb {
 
 template <int MODE>
@@ -124,31 +120,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
     // hidden chunk pj in four stages (they go between the MFMA runs of the next chunk, one per run): A = softplus (+ its sigmoid in
     // MODE 5) of a value pair, B = exact three-way split into the next layer's operand registers
     float ev0[2], ev1[2];
-#if SX_PK
-    // the same arithmetic on value PAIRS: v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 round like their scalar forms (bit-identical),
-    // the transcendentals and the selects stay per value
-    auto stage_a = [&](const SxAcc& a, int q, f4& sg) {
-      const f2 c0 = q ? f2{a.c0[2], a.c0[3]} : f2{a.c0[0], a.c0[1]};
-      const f2 c1 = q ? f2{a.c1[2], a.c1[3]} : f2{a.c1[0], a.c1[1]};
-      const f2 c2 = q ? f2{a.c2[2], a.c2[3]} : f2{a.c2[0], a.c2[1]};
-      const f2 k11 = f2{C11, C11};
-      const f2 z = __builtin_elementwise_fma(__builtin_elementwise_fma(c2, k11, c1), k11, c0);
-      // softplus100_stable (mlp_engine.h) on a value pair
-      const f2 t = f2{-__builtin_fabsf(z[0]), -__builtin_fabsf(z[1])} * SP_T_PER_Z;
-      const f2 e = f2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-      const f2 u = e + 1.0f;
-      const f2 lg = f2{__builtin_amdgcn_logf(u[0]), __builtin_amdgcn_logf(u[1])};
-      if constexpr (STORE) {
-        const f2 r = f2{__builtin_amdgcn_rcpf(u[0]), __builtin_amdgcn_rcpf(u[1])};
-        sg[2 * q] = (z[0] > 0.0f ? 1.0f : e[0]) * r[0];
-        sg[2 * q + 1] = (z[1] > 0.0f ? 1.0f : e[1]) * r[1];
-      }
-      f2 v = __builtin_elementwise_fma(lg, f2{SP_LN2_OVER_100, SP_LN2_OVER_100}, f2{__builtin_fmaxf(z[0], 0.0f), __builtin_fmaxf(z[1], 0.0f)});
-      if (SKIPOUT) v = v * inv_sqrt2;
-      ev0[q] = v[0];
-      ev1[q] = v[1];
-    };
-#else
+    // (the same arithmetic on value pairs, v_pk_* f32, measured 1 % slower and was removed: profiles/r03_sdf_x6_ablation.md)
     auto stage_a = [&](const SxAcc& a, int q, f4& sg) {
       float s0, s1;
       // the overflow-free form (mlp_engine.h: max(z, 0) + a correction <= 0.0069 from the hardware exp2 / log2)
@@ -162,7 +134,6 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
       ev0[q] = v0;
       ev1[q] = v1;
     };
-#endif
     auto stage_b = [&](int pj, int q) { put_pair(ev0[q], ev1[q], yh[pj >> 1], ym[pj >> 1], yl[pj >> 1], (pj & 1) * 2 + q, std::true_type{}); };
     auto store_sig = [&](int pj, const f4& sg) {
       if constexpr (STORE) sig[((rrow >> 4) * 8 + lrt) * (16L * 64) + pj * 64 + lane] = sg;

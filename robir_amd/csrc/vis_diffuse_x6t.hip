@@ -37,9 +37,6 @@ constexpr int XT_PIECES = 6;             // 4 KB rows (1 KB per wave) of one chu
 #ifndef XT_FP8
 #define XT_FP8 1
 #endif
-#ifndef XT_PINGPONG
-#define XT_PINGPONG 0
-#endif
 
 __device__ __forceinline__ void xt_dma16(const f4* gbase_uniform, unsigned lane_byte_off, unsigned lds_byte_uniform) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_byte_uniform), "v"(lane_byte_off),
@@ -410,14 +407,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #define XT_COPY(I) do { } while (0)
 #else
   // pieces 0..5 are issued in this order in the chunk's second half with no other LDS-DMA between them: M0 is set by pieces 0 and 4
-  // and carried (two scalar issue slots less for the other four)
-#ifdef XT_M0_EVERY_PIECE             // A/B switch: M0 written by every piece (the round-4 form before this change)
-#define XT_COPY(I)                                                                  \
-  do {                                                                              \
-    if ((I) < 4) xt_dma16_imm<((I) & 3) * 1024>(dsrc, voff_a, ddst);                \
-    else xt_dma16_imm<((I) & 3) * 1024>(dsrc, voff_b, ddst + 4096u);                \
-  } while (0)
-#else
+  // and carried (two scalar issue slots less for the other four; round 4's M0 write per piece, 98.3 against 98.1 ms, was removed: DESIGN
+  // section 5.0)
 #define XT_COPY(I)                                                                  \
   do {                                                                              \
     if ((I) == 0) xt_dma16_imm<0>(dsrc, voff_a, ddst);                              \
@@ -425,7 +416,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     else if ((I) == 4) xt_dma16_imm<0>(dsrc, voff_b, ddst + 4096u);                 \
     else xt_dma16_m0kept<((I) & 3) * 1024>(dsrc, voff_b);                           \
   } while (0)
-#endif
 #endif
 #define XT_FENCE __builtin_amdgcn_sched_barrier(0)
 #ifdef XT_ABL_NOLDS                   // timing ablation (wrong results): no fragment reads
@@ -479,17 +469,16 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           XT_RUN(acc[1].c0, wh, X.h[1]);                       // 4
           if (H == 0) XT_EP(3); else XT_COPY(0);
           XT_FENCE;
-#ifndef XT_FP8_EP_AT6
-#define XT_FP8_EP_AT6 1     // the filler of position 5 (which also carries the four h refills) behind the bf8 MFMA of position 6: a single 32-cycle MFMA shadows its fillers better than the last of a run of four (-0.8 %, bit-identical); 0: at position 5
-#endif
           XT_RUN_REFILL(acc[1].c1, wh, X.m[1], 0);             // 5: the f16 h fragments' last use
-          if (!XT_FP8_EP_AT6) { if (H == 0) XT_EP(4); else XT_COPY(1); }
           XT_FENCE;
+          // the filler of position 5 (which also carries the four h refills) behind the bf8 MFMA of position 6: a single 32-cycle MFMA
+          // shadows its fillers better than the last of a run of four (-0.8 %, bit-identical; the same move for the fillers of positions
+          // 9 / 11, behind the bf8 MFMAs of positions 11 / 12, measured worse and was removed: commit bd70337)
           XT_MFMA8(acc[1].c2, w8h, X.l8[1][H]);                // 6: the bf8 h fragment's last use
 #ifndef XT_ABL_NOLDS
           XT_LOAD8(w8h, nfrag, (1 - H) * 768 + 512)
 #endif
-          if (XT_FP8_EP_AT6) { if (H == 0) XT_EP(4); else XT_COPY(1); }
+          if (H == 0) XT_EP(4); else XT_COPY(1);
           XT_FENCE;
 #else
           XT_RUN(acc[0].c2, wh, X.l[0]);                       // 3
@@ -510,23 +499,19 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           XT_RUN(acc[0].c2, wm, X.m[0]);                       // 8
           if (H == 0) XT_EP(6); else XT_COPY(3);
           XT_FENCE;
-#ifndef XT_FP8_EP_AT12
-#define XT_FP8_EP_AT12 0    // 1: the fillers of positions 9 / 11 behind the bf8 MFMAs of positions 11 / 12 (XT_FP8 only)
-#endif
           XT_RUN(acc[1].c1, wm, X.h[1]);                       // 9
-          if (!(XT_FP8 && XT_FP8_EP_AT12)) { if (H == 0) XT_EP(7); else XT_COPY(4); }
+          if (H == 0) XT_EP(7); else XT_COPY(4);
           XT_FENCE;
           XT_RUN_REFILL(acc[1].c2, wm, X.m[1], 1);             // 10: the m fragments' last use
           XT_FENCE;
 #if XT_FP8
           XT_MFMA8(acc[0].c2, w8l, X.h8[0][H]);                // 11: l.xh as one bf8 MFMA
-          if (XT_FP8_EP_AT12) { if (H == 0) XT_EP(7); else XT_COPY(4); } else { if (H == 0) XT_EP(8); else XT_COPY(5); }
+          if (H == 0) XT_EP(8); else XT_COPY(5);
           XT_FENCE;
           XT_MFMA8(acc[1].c2, w8l, X.h8[1][H]);                // 12: the bf8 l fragment's last use
 #ifndef XT_ABL_NOLDS
           XT_LOAD8(w8l, nfrag, (1 - H) * 768 + 640)
 #endif
-          if (XT_FP8_EP_AT12) { if (H == 0) XT_EP(8); else XT_COPY(5); }
           XT_FENCE;
 #else
           XT_RUN(acc[0].c2, wl, X.h[0]);                       // 11
@@ -550,12 +535,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #pragma unroll
       for (int s = 0; s < 12; ++s) ep_slot(Y, s, 15);
     };
-#if XT_PINGPONG     // three copies of the layer body, the operand sets alternate: no register moves at a layer's end
-    layer(0, P, Q);
-    layer(1, Q, P);
-    layer(2, P, Q);
-    Ops& HX = Q;
-#else
+    // the next layer's operands move into P at a layer's end (three copies of the layer body with alternating sets spilled, with twice
+    // the code, and were removed: DESIGN section 5.3)
 #pragma unroll 1
     for (int l = 0; l < 3; ++l) {
       layer(l, P, Q);
@@ -579,8 +560,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         }
 #endif
     }
-    Ops& HX = P;
-#endif
     // ---- head: chunk 48 from its resident LDS copy; `bias` holds its bias (fetched by the last chunk of layer 2) and the fragment
     // window already holds the first half of the next round's chunk 0.  Next round's rows are requested first: they arrive under
     // the head's MFMAs (clamped to this round's samples after the final round: harmless)
@@ -602,10 +581,10 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         const u4 fh = hw[XT_F16OFF(kb, 0)], fm = hw[XT_F16OFF(kb, 1)];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          XT_MFMA(acc[t].c0, fh, HX.h[t][kb]);
-          XT_MFMA(acc[t].c1, fh, HX.m[t][kb]);
-          XT_MFMA(acc[t].c1, fm, HX.h[t][kb]);
-          XT_MFMA(acc[t].c2, fm, HX.m[t][kb]);
+          XT_MFMA(acc[t].c0, fh, P.h[t][kb]);
+          XT_MFMA(acc[t].c1, fh, P.m[t][kb]);
+          XT_MFMA(acc[t].c1, fm, P.h[t][kb]);
+          XT_MFMA(acc[t].c2, fm, P.m[t][kb]);
         }
       }
 #pragma unroll
@@ -615,8 +594,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         XT_LOAD8(f8l, hw, hf * 768 + 640)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8h, HX.l8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
-          acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8l, HX.h8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
+          acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8h, P.l8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
+          acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8l, P.h8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
         }
       }
 #else
@@ -624,12 +603,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         const u4 fh = hw[(kb * 3 + 0) * 64], fm = hw[(kb * 3 + 1) * 64], fl = hw[(kb * 3 + 2) * 64];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          XT_MFMA(acc[t].c0, fh, HX.h[t][kb]);
-          XT_MFMA(acc[t].c1, fh, HX.m[t][kb]);
-          XT_MFMA(acc[t].c2, fh, HX.l[t][kb]);
-          XT_MFMA(acc[t].c1, fm, HX.h[t][kb]);
-          XT_MFMA(acc[t].c2, fm, HX.m[t][kb]);
-          XT_MFMA(acc[t].c2, fl, HX.h[t][kb]);
+          XT_MFMA(acc[t].c0, fh, P.h[t][kb]);
+          XT_MFMA(acc[t].c1, fh, P.m[t][kb]);
+          XT_MFMA(acc[t].c2, fh, P.l[t][kb]);
+          XT_MFMA(acc[t].c1, fm, P.h[t][kb]);
+          XT_MFMA(acc[t].c2, fm, P.m[t][kb]);
+          XT_MFMA(acc[t].c2, fl, P.h[t][kb]);
         }
       }
 #endif

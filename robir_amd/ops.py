@@ -1086,7 +1086,7 @@ def cesr_net_x6_points(x, M, kind, blob, n_label=1):
     return Y
 
 
-CESR_F16_TILES = int(os.environ.get("ROBIR_CESR_F16_TILES", "3"))        # 16-row tiles per wave of the f16 CESR kernel (what the library is built with: csrc/cesr_f16.hip FX_TILES)
+CESR_F16_TILES = 3        # 16-row tiles per wave of the f16 CESR kernel (the one count the library carries: csrc/cesr_f16.hip FX_NTILES)
 
 
 def cesr_net_f16_points(x, M, kind, blob, n_label=1):
