@@ -296,6 +296,24 @@ int rb_sg_shade(const float* normal, const float* view, const float* lgt, int pe
                 const float* rough, const float* albedo, const float* metallic, const float* light_vis,
                 const float* bvis, const float* indir_integral, int lin_diff, long n, float* out_rgb, float* out_spec,
                 float* out_diff, float* out_shadow, rb_stream_t stream);
+/* Reverse mode of rb_sg_shade (csrc/sg_shade_bwd.hip): gradients of <g_spec, out_spec> + <g_diff, out_diff>.  The first fourteen arguments are
+ * rb_sg_shade's; out_spec / out_diff are what that call returned (the clamp at zero: a stored output > 0 passes its gradient, a stored 0 is
+ * re-evaluated -- a clamped negative sum passes nothing, an exact zero passes like torch.clamp), g_spec / g_diff [n,3] the upstream gradients
+ * (fold a gradient of out_rgb into both).  Every d_* is optional (NULL = not wanted): d_rough [n], d_albedo [n,3], d_metallic [n] (needs
+ * metallic), d_bvis [n], d_light_vis [n,M] (needs light_vis), d_indir_integral [n,3] (needs indir_integral; the SG diffuse sum then gets no
+ * gradient, it was overwritten), d_lgt [M,7] summed over the points (per_point_lgt=0) or [n,M,7], d_f0 [1] summed over the points.  normal,
+ * view and the shadow output carry no gradient.  The two sums over points use no atomics and are bit-reproducible: rb_sg_shade_bwd_groups(n)
+ * = min(ceil(n/4), 512) workgroups of four waves (wave w of workgroup b: points 4b+w, 4b+w+4G, ...) each store one fp64 slab into `scratch`,
+ * a second kernel adds the slabs in order.  scratch: DEVICE memory, 8-byte aligned, at least rb_sg_shade_bwd_scratch_floats(M)
+ * = 2 * 512 * (7 M + 1) floats, needed when d_f0 or the shared light's d_lgt is wanted (else NULL / 0); nothing is kept between calls. */
+int rb_sg_shade_bwd(const float* normal, const float* view, const float* lgt, int per_point_lgt, int M, const float* f0,
+                    const float* rough, const float* albedo, const float* metallic, const float* light_vis, const float* bvis,
+                    const float* indir_integral, int lin_diff, long n, const float* out_spec, const float* out_diff,
+                    const float* g_spec, const float* g_diff, float* d_rough, float* d_albedo, float* d_metallic, float* d_bvis,
+                    float* d_light_vis, float* d_indir_integral, float* d_lgt, float* d_f0, float* scratch, long scratch_floats,
+                    rb_stream_t stream);
+long rb_sg_shade_bwd_scratch_floats(int M);
+int rb_sg_shade_bwd_groups(long n);
 /* render_envmap_sg (model/sg_render.py:26-42): rgb[n,3] = sum_k |mu_k| exp(|lambda_k| (d . lobe_k/|lobe_k| - 1)), lgt[M,7] */
 int rb_envmap_sg(const float* lgt, int M, const float* dirs, long n, float* rgb, rb_stream_t stream);
 /* render_envmap (model/sg_render.py:45-59): bilinear lookup of env[H,W,3] (lat-long, row-major) along dirs[n,3]; same

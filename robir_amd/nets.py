@@ -6,9 +6,11 @@ model/sg_envmap_material.py:40-275 (SparseAE, EnvmapMaterialNetwork),
 model/neus_model.py:312-438,489-560,644-650,682-884 (SDFNetwork, RenderingNetwork, SingleVarianceNetwork,
 NeuSModel, ImplicitNetworkMy).
 
-Forward-only: the kernels carry no autograd.  A forward pass of a module that is in training mode, with grad enabled and
+Forward-only: the network kernels carry no autograd.  A forward pass of a module that is in training mode, with grad enabled and
 a parameter that requires grad, raises ForwardOnlyError (`forward_only_guard`; the drop-in is for inference /
---plot_only rendering) instead of handing detached outputs to a loss.
+--plot_only rendering) instead of handing detached outputs to a loss.  Material NETWORKS therefore still train on
+the reference's modules; what IS differentiable on the HIP path is the SG shading of their outputs (robir_amd/sg_autograd.py,
+sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis).
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """

@@ -702,6 +702,50 @@ def sg_shade(normal, view, lgt, f0, rough, albedo, bvis, light_vis=None, metalli
     return rgb, spec, diff, shadow
 
 
+def sg_shade_backward(normal, view, lgt, f0, rough, albedo, bvis, spec, diff, g_spec, g_diff, light_vis=None, metallic=None,
+                      indir_integral=None, lin_diff=False, want=("lgt", "f0", "rough", "albedo", "metallic", "bvis", "light_vis", "indir_integral")):
+    """Reverse mode of sg_shade (rb_sg_shade_bwd): gradients of <g_spec, spec> + <g_diff, diff> for the inputs named in `want`, as a dict.
+    spec / diff are sg_shade's own outputs for the same inputs (the clamp masks).  lgt [M,7] -> 'lgt' [M,7] summed over the points;
+    [n,M,7] -> [n,M,7]; 'f0' [1] summed over the points.  Allocates the wanted outputs and the reduction scratch, nothing else: no
+    [n,M] tensor unless 'light_vis' is asked for.  A name whose input is absent (metallic, light_vis, indir_integral = None) is skipped."""
+    normal, view, lgt, albedo = _f32(normal), _f32(view), _f32(lgt), _f32(albedo)
+    rough, bvis = _f32(rough).reshape(-1), _f32(bvis).reshape(-1)
+    spec, diff, g_spec, g_diff = _f32(spec), _f32(diff), _f32(g_spec), _f32(g_diff)
+    n = normal.shape[0]
+    per_point = lgt.dim() == 3
+    M = lgt.shape[-2]
+    dev = normal.device
+    f0 = (f0.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous() if isinstance(f0, torch.Tensor)
+          else torch.full((1,), float(f0), device=dev))
+    metallic = _f32(metallic).reshape(-1) if metallic is not None else None
+    light_vis = _f32(light_vis) if light_vis is not None else None
+    indir_integral = _f32(indir_integral) if indir_integral is not None else None
+    shapes = {"lgt": tuple(lgt.shape), "f0": (1,), "rough": (n,), "albedo": (n, 3), "bvis": (n,)}
+    if metallic is not None:
+        shapes["metallic"] = (n,)
+    if light_vis is not None:
+        shapes["light_vis"] = (n, M)
+    if indir_integral is not None:
+        shapes["indir_integral"] = (n, 3)
+    alloc = torch.zeros if n == 0 else torch.empty           # n > 0: the kernels store every element of every wanted output
+    out = {k: alloc(shapes[k], dtype=torch.float32, device=dev) for k in want if k in shapes}
+    scratch, ns = None, 0
+    if "f0" in out or ("lgt" in out and not per_point):
+        ns = int(_lib.lib().rb_sg_shade_bwd_scratch_floats(c_int(M)))
+        scratch = torch.empty(ns, dtype=torch.float32, device=dev)
+    call("rb_sg_shade_bwd", ptr(normal), ptr(view), ptr(lgt), c_int(1 if per_point else 0), c_int(M), ptr(f0), ptr(rough), ptr(albedo),
+         ptr(metallic), ptr(light_vis), ptr(bvis), ptr(indir_integral), c_int(1 if lin_diff else 0), c_long(n), ptr(spec), ptr(diff),
+         ptr(g_spec), ptr(g_diff), ptr(out.get("rough")), ptr(out.get("albedo")), ptr(out.get("metallic")), ptr(out.get("bvis")),
+         ptr(out.get("light_vis")), ptr(out.get("indir_integral")), ptr(out.get("lgt")), ptr(out.get("f0")), ptr(scratch), c_long(ns),
+         stream_ptr())
+    return out
+
+
+def sg_shade_backward_groups(n):
+    """Workgroups of rb_sg_shade_bwd's persistent grid for n points (four waves each; wave w of workgroup b: points 4b+w, 4b+w+4G, ...)."""
+    return int(_lib.lib().rb_sg_shade_bwd_groups(c_long(n)))
+
+
 # ------------------------------------------------------------------------------------------------ octree
 def _host3(a, ctype):
     import numpy as np

@@ -12,7 +12,8 @@ render_chunks(): the same arithmetic for MANY 1024-pixel chunks in one pass -- e
 (the octree tracer's active-ray schedule, utils/octree.py:545-549, and the specular-cone minimum,
 model/sg_render.py:222) stay per chunk.  Results are what the reference produces rendering the chunks one by one.
 
-Forward only (no autograd through the kernels).
+Forward only: IDRNetwork.forward runs under no_grad and nothing here differentiates a network.  The SG shading it calls is differentiable
+on its own (sg_render.render_with_all_sg with grad mode on, robir_amd/sg_autograd.py): geometry frozen, sampled visibilities constant.
 """
 import math
 

@@ -10,13 +10,22 @@ Extensions (keyword-only, ignored by reference callers):
             batch-global minimum in the specular cone (sg_render.py:222), i.e. exactly what the reference computes
             when it renders the chunks one after another;
   stats     dict receiving 'diffuse_vis_evals' (device counter tensor).
+
+Gradients.  render_with_sg / render_with_all_sg are differentiable on the HIP path with respect to lgtSGs, indir_lgtSGs,
+specular_reflectance, roughness, diffuse_albedo, metallic, indir_integral and (CESR) the predicted diffuse_vis: when grad mode is on and one
+of them requires grad, the shading runs through sg_autograd.SgShadeFn (rb_sg_shade + rb_sg_shade_bwd); otherwise exactly the forward-only
+path.  The SAMPLED visibilities are constants of the backward: the light visibility as in the reference (sampled under no_grad there), the
+specular visibility as a deliberate difference -- the reference lets a gradient leak from the sample weights into roughness (and, outside
+`testing`, through the visibility MLP into the sample directions); this build stops it there.  points, normal and viewdirs are not
+differentiable: one of them requiring grad (grad mode on) raises NotImplementedError.  vis_shadow carries no gradient; `supervise` is built
+from torch ops and needs nothing.
 """
 import math
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, sg_autograd
 from .nets import VisNetwork
 from .octree_tracing import OctreeVisModel
 
@@ -257,7 +266,10 @@ def render_with_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, rough
                    stats=None):
     """sg_render.py:343-565.  viewdirs [n,3], or [V,n,3] for the MULTI_VIEW form (_render_with_sg_multi_view).  lgtSGs [n,M,7] (or [M,7]).  fun_spec=True (sg_render.py:413,544-551): the specular term
     comes back as a function of a roughness tensor (its specular visibility is sampled at every call, like the reference's closure;
-    `draws=` pins the samples), `sg_rgb` is then the diffuse term alone."""
+    `draws=` pins the samples), `sg_rgb` is then the diffuse term alone.
+    Differentiable (module docstring, 'Gradients'): lgtSGs, specular_reflectance, roughness -- also the closure's argument --,
+    diffuse_albedo, metallic, indir_integral, diffuse_vis; the sampled visibilities are constants; points / normal / viewdirs refuse."""
+    sg_autograd.refuse_geometry_grad(points=points, normal=normal, viewdirs=viewdirs)
     if viewdirs.dim() == 3:
         return _render_with_sg_multi_view(points, normal, viewdirs, lgtSGs, specular_reflectance, roughness, diffuse_albedo, comp_vis,
                                           VisModel, fun_spec, lin_diff, testing, indir_integral, metallic, diffuse_vis, prefit,
@@ -272,7 +284,10 @@ def render_with_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, rough
     rough = roughness.float().contiguous().reshape(-1)
     f0 = specular_reflectance          # stays on the device: rb_sg_shade reads the scalar itself
     shared = lgtSGs.dim() == 2 or (lgtSGs.stride(0) == 0)
-    lgt_first = (lgtSGs if lgtSGs.dim() == 2 else lgtSGs[0]).float().contiguous()
+    if shared and sg_autograd.wants_grad(lgtSGs):       # the [M,7] tensor behind an expanded view: its gradient is summed on the device
+        lgt_first = sg_autograd.shared_light(lgtSGs).float().contiguous()
+    else:
+        lgt_first = (lgtSGs if lgtSGs.dim() == 2 else lgtSGs[0]).float().contiguous()
     light_vis = None
     supervise = torch.zeros((), device=dev)
     if comp_vis:
@@ -294,19 +309,25 @@ def render_with_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, rough
                 light_vis = pred
     lgt = lgt_first if shared else lgtSGs.float().contiguous()
 
+    def sg_shade(rough_, bvis):
+        """-> rgb, spec, diff, shadow: through the autograd Function when a differentiable input asks for a gradient, else the plain op"""
+        if sg_autograd.wants_grad(lgt, f0, rough_, diffuse_albedo, metallic, indir_integral, light_vis):
+            return sg_autograd.sg_shade(nrm, vd, lgt, f0, rough_, diffuse_albedo, bvis, light_vis=light_vis, metallic=metallic,
+                                        indir_integral=indir_integral, lin_diff=lin_diff)
+        return ops.sg_shade(nrm, vd, lgt, f0, rough_, diffuse_albedo, bvis, light_vis=light_vis, metallic=metallic,
+                            indir_integral=indir_integral, lin_diff=lin_diff, want_shadow=True)
+
     def shade(rough_, spec_draws):
         u_t, u_p = spec_draws.get("svis_theta"), spec_draws.get("svis_phi")
         if u_t is None:
             u_t, u_p = _rand((n, 8), dev), _rand((n, 8), dev)
         bvis = _specular_vis_core(pts, nrm, vd, VisModel, rough_, u_t.to(dev), u_p.to(dev), testing, not comp_vis, argmax_vis,
                                   cid, C)
-        return ops.sg_shade(nrm, vd, lgt, f0, rough_, diffuse_albedo, bvis, light_vis=light_vis, metallic=metallic,
-                            indir_integral=indir_integral, lin_diff=lin_diff, want_shadow=True)
+        return sg_shade(rough_, bvis)           # bvis: sampled by kernels, a constant of the backward
 
     if fun_spec:
         # the diffuse term and the shadow do not depend on the specular visibility: one shading pass with bvis = 1 gives them
-        _, _, diff, shadow = ops.sg_shade(nrm, vd, lgt, f0, rough, diffuse_albedo, torch.ones(n, device=dev), light_vis=light_vis,
-                                          metallic=metallic, indir_integral=indir_integral, lin_diff=lin_diff, want_shadow=True)
+        _, _, diff, shadow = sg_shade(rough, torch.ones(n, device=dev))
 
         def specular_rgb_fn(roughness, draws=None):
             return shade(roughness.float().contiguous().reshape(-1), draws or {})[1]
@@ -340,7 +361,11 @@ def _render_with_sg_multi_view(points, normal, viewdirs, lgtSGs, specular_reflec
     alb = diffuse_albedo.float().repeat(V, 1)
     met = metallic.float().reshape(n, -1).repeat(V, 1) if metallic is not None else None
     shared = lgtSGs.dim() == 2 or lgtSGs.stride(0) == 0
-    lgt = ((lgtSGs if lgtSGs.dim() == 2 else lgtSGs[0]) if shared else lgtSGs.repeat(V, 1, 1)).float().contiguous()
+    if shared:
+        lgt = (sg_autograd.shared_light(lgtSGs) if sg_autograd.wants_grad(lgtSGs) else (lgtSGs if lgtSGs.dim() == 2 else lgtSGs[0]))
+        lgt = lgt.float().contiguous()
+    else:
+        lgt = lgtSGs.repeat(V, 1, 1).float().contiguous()
 
     def specular_rgb_fn(roughness, draws=draws):
         draws = draws or {}
@@ -350,6 +375,8 @@ def _render_with_sg_multi_view(points, normal, viewdirs, lgtSGs, specular_reflec
             u_t, u_p = _rand((n, 16), dev), _rand((n, 16), dev)      # nsamp = 16 in this branch (:467)
         bvis = _specular_vis_core(pts, nrm, vd, VisModel, rough, u_t.to(dev).repeat(V, 1), u_p.to(dev).repeat(V, 1), testing, False,
                                   True, None, 1)
+        if sg_autograd.wants_grad(lgt, specular_reflectance, rough, alb, met):
+            return sg_autograd.sg_shade(nrm, vd, lgt, specular_reflectance, rough, alb, bvis, metallic=met, lin_diff=lin_diff)[1].reshape(V, n, 3)
         return ops.sg_shade(nrm, vd, lgt, specular_reflectance, rough, alb, bvis, metallic=met, lin_diff=lin_diff)[1].reshape(V, n, 3)
 
     if fun_spec:
@@ -363,7 +390,7 @@ def render_with_all_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, r
                        testing=False, metallic=None, diffuse_vis=None, prefit=False, argmax_vis=False, *, draws=None,
                        chunk_id=None, n_chunks=1, stats=None):
     """sg_render.py:304-337: direct pass (light visibility) + indirect pass (per-point lobes, inverted specular
-    visibility, diffuse := indir_integral)."""
+    visibility, diffuse := indir_integral).  Differentiable as render_with_sg is (module docstring, 'Gradients')."""
     draws = draws or {}
     d_dir = {k: draws[k] for k in ("dvis_theta", "dvis_phi") if k in draws}
     if "svis_theta_dir" in draws:
