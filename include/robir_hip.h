@@ -521,6 +521,48 @@ int rb_neus_core_aux(const float* sdf, long sdf_stride, const float* pts, const 
 int rb_sample_dirs(const float* normals, const float* theta, const float* phi, long n, float* dirs, rb_stream_t stream);
 int rb_intersect_sphere(const float* origins, const float* dirs, long n, float radius, float* out, rb_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Isosurface extraction: lattice of SDF values -> indexed triangle mesh (robir_amd/csrc/mesh.hip; additive, ABI 8).
+ * Replaces: neus/optimization/extraction.py:12-49 (extract_fields' host copies, mcubes.marching_cubes, trimesh).
+ * Marching tetrahedra on the Kuhn split of every cell; the tables are generated at compile time (no marching-cubes table).
+ *   field f[nx][ny][nz] fp32, z fastest, nx, ny, nz >= 2; lattice vertex v = (ix*ny + iy)*nz + iz at (xs[ix], ys[iy], zs[iz]);
+ *   a lattice vertex is INSIDE iff f < iso.  It owns the edges to v + d, slot 0..6: d = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1)
+ *   (0,1,1) (1,1,1), where the far end is in the lattice.  A mesh vertex sits on every owned edge whose ends differ in inside-ness,
+ *   at a + t (b - a) per component, t = (iso - f_a) / (f_b - f_a), a = the owner; plain fp32, no contraction.
+ *   Cell = six tetrahedra, one per permutation (p,q,r) of the axes in lexicographic order: tet corners 0..3 = 000, e_p, e_p+e_q, 111.
+ *   Per tetrahedron and inside mask (bit i = tet corner i): one corner a alone on its side, the others o1 < o2 < o3: the triangle of
+ *   the edges (a,o1) (a,o2) (a,o3); two inside a < b, two outside c < d: the quad (a,c) (a,d) (b,d) (b,c) as (q0,q1,q2), (q0,q2,q3);
+ *   the 2nd and 3rd vertex swapped where needed so that (B-A)x(C-A) points from inside to outside (towards increasing f).
+ * ORDER of the output (deterministic: no atomics, the same inputs give the same bytes): mesh vertices by owner linear index, then
+ * edge slot; faces by cell linear index (that of the cell's lowest corner), then tetrahedron, then triangle.
+ * Protocol (the one host read sits between the entry points):
+ *   rb_mesh_groups         number G of workgroups (runs of 256 lattice vertices) of the three kernels; -1 on error
+ *   rb_mesh_count          counts[G][2] int32 = (mesh vertices on owned edges, triangles of owned cells) per workgroup
+ *   host                   exclusive prefix sums (int64) of the two columns, the two grand totals V and F; allocate
+ *   rb_mesh_emit_vertices  verts[V][3] fp32 and vbase[nx*ny*nz] int32 = index of the lattice vertex's first owned mesh vertex
+ *   rb_mesh_emit_faces     faces[F][3] int32; the mesh vertex on slot k of owner v is vbase[v] + popcount(mask_v & ((1<<k)-1))
+ * V or F >= 2^31 is an error; V == 0 / F == 0 returns 0 without a launch.
+ * rb_mesh_table: HOST int[6*16*7], per (tetrahedron, mask): triangle count, then 6 tet edge ids (0..5 = corner pairs 01 02 03 12
+ * 13 23; -1 padding) -- the generated table, for tests.
+ * Block-sparse fill of the lattice: blocks of B (2..16) lattice vertices per axis, the last block of an axis shorter; block id
+ * (bx*nby + by)*nbz + bz with nb* = ceil(n* / B); vertex l of a block = (lx*B + ly)*B + lz.
+ *   rb_mesh_block_points   pts[nb*B^3][3]: coordinates of the listed blocks' vertices (ragged blocks clamp to the last lattice vertex)
+ *   rb_mesh_block_store    field <- vals[nb*B^3] at the listed blocks' in-lattice vertices
+ *   rb_mesh_block_fill     field <- vals[nb] (one value per block) at the listed blocks' in-lattice vertices
+ * ------------------------------------------------------------------------------------------------------------ */
+long rb_mesh_groups(int nx, int ny, int nz);
+int rb_mesh_table(int* table /* HOST */);
+int rb_mesh_count(const float* f, int nx, int ny, int nz, float iso, int* counts, long n_counts, rb_stream_t stream);
+int rb_mesh_emit_vertices(const float* f, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float iso,
+                          const long* group_base, long V, float* verts, int* vbase, rb_stream_t stream);
+int rb_mesh_emit_faces(const float* f, int nx, int ny, int nz, float iso, const long* group_base, const int* vbase, long V, long F,
+                       int* faces, rb_stream_t stream);
+int rb_mesh_block_points(const int* blocks, long nb, int B, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz,
+                         float* pts, long n_pts, rb_stream_t stream);
+int rb_mesh_block_store(const int* blocks, long nb, int B, const float* vals, long n_vals, int nx, int ny, int nz, float* field,
+                        rb_stream_t stream);
+int rb_mesh_block_fill(const int* blocks, long nb, int B, const float* vals, int nx, int ny, int nz, float* field, rb_stream_t stream);
+
 /* Host-only helper (no GPU work): one PIZ-compressed OpenEXR chunk -> 16-bit words, channel-major
  * ([channel][line][pixel][word]); chan = n_ch rows of (pixels per line, lines, words per pixel: 1 HALF, 2 FLOAT/UINT).
  * Used by robir_amd/exr.py to read the relighting environment maps that EnvmapMaterialNetwork.load_light

@@ -47,7 +47,7 @@ def _load(path, what):
     L = ctypes.CDLL(path)
     L.rb_last_error.restype = ctypes.c_char_p
     for name in ("rb_packed_layer_floats", "rb_packed_layer_x6_floats", "rb_sdf_value_grad_scratch_floats",
-                 "rb_sdf_value_grad_f32_scratch_floats", "rb_sg_shade_bwd_scratch_floats"):
+                 "rb_sdf_value_grad_f32_scratch_floats", "rb_sg_shade_bwd_scratch_floats", "rb_mesh_groups"):
         if hasattr(L, name):
             getattr(L, name).restype = ctypes.c_long
     if L.rb_abi_version() != ABI_VERSION:

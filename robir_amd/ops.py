@@ -1301,3 +1301,77 @@ def intersect_sphere(origins, dirs, radius):
     out = torch.empty(n, 3, dtype=torch.float32, device=origins.device)
     call("rb_intersect_sphere", ptr(origins), ptr(dirs), c_long(n), c_float(radius), ptr(out), stream_ptr())
     return out
+
+
+# ----------------------------------------------------------------------------------------- isosurface extraction (csrc/mesh.hip)
+def mesh_groups(nx, ny, nz):
+    L = _lib.lib()
+    g = L.rb_mesh_groups(c_int(nx), c_int(ny), c_int(nz))
+    if g < 0:
+        raise _lib.RobirHipError(f"rb_mesh_groups failed: {L.rb_last_error().decode()}")
+    return int(g)
+
+
+def mesh_table():
+    """The generated marching-tetrahedra table as a [6,16,7] int list: per (tetrahedron, inside mask) the triangle count and six tet edge ids."""
+    buf = (ctypes.c_int * (6 * 16 * 7))()
+    call("rb_mesh_table", buf)
+    return [[list(buf[(t * 16 + m) * 7:(t * 16 + m) * 7 + 7]) for m in range(16)] for t in range(6)]
+
+
+def mesh_count(field, iso):
+    """field [nx,ny,nz] -> counts [G,2] int32: mesh vertices and triangles per workgroup of 256 lattice vertices."""
+    field = _f32(field)
+    nx, ny, nz = field.shape
+    counts = torch.empty(mesh_groups(nx, ny, nz), 2, dtype=torch.int32, device=field.device)
+    call("rb_mesh_count", ptr(field), c_int(nx), c_int(ny), c_int(nz), c_float(iso), ptr(counts), c_long(counts.numel()), stream_ptr())
+    return counts
+
+
+def mesh_emit_vertices(field, xs, ys, zs, iso, group_base, V):
+    """group_base [G] int64 exclusive prefix of the vertex counts -> (verts [V,3], vbase [nx,ny,nz] int32)."""
+    field, xs, ys, zs = _f32(field), _f32(xs), _f32(ys), _f32(zs)
+    nx, ny, nz = field.shape
+    assert (xs.numel(), ys.numel(), zs.numel()) == (nx, ny, nz) and group_base.dtype == torch.int64
+    verts = torch.empty(V, 3, dtype=torch.float32, device=field.device)
+    vbase = torch.empty(nx, ny, nz, dtype=torch.int32, device=field.device)
+    call("rb_mesh_emit_vertices", ptr(field), ptr(xs), ptr(ys), ptr(zs), c_int(nx), c_int(ny), c_int(nz), c_float(iso), ptr(group_base),
+         c_long(V), ptr(verts), ptr(vbase), stream_ptr())
+    return verts, vbase
+
+
+def mesh_emit_faces(field, iso, group_base, vbase, V, F):
+    field = _f32(field)
+    nx, ny, nz = field.shape
+    assert group_base.dtype == torch.int64 and vbase.dtype == torch.int32 and vbase.numel() == field.numel()
+    faces = torch.empty(F, 3, dtype=torch.int32, device=field.device)
+    call("rb_mesh_emit_faces", ptr(field), c_int(nx), c_int(ny), c_int(nz), c_float(iso), ptr(group_base), ptr(vbase), c_long(V), c_long(F),
+         ptr(faces), stream_ptr())
+    return faces
+
+
+def mesh_block_points(blocks, B, xs, ys, zs):
+    """blocks [nb] int32 block ids -> pts [nb*B^3, 3]."""
+    assert blocks.dtype == torch.int32
+    n = blocks.numel() * B ** 3
+    pts = torch.empty(n, 3, dtype=torch.float32, device=xs.device)
+    call("rb_mesh_block_points", ptr(blocks), c_long(blocks.numel()), c_int(B), ptr(_f32(xs)), ptr(_f32(ys)), ptr(_f32(zs)),
+         c_int(xs.numel()), c_int(ys.numel()), c_int(zs.numel()), ptr(pts), c_long(n), stream_ptr())
+    return pts
+
+
+def mesh_block_store(blocks, B, vals, field):
+    assert blocks.dtype == torch.int32 and field.dtype == torch.float32 and field.is_contiguous()
+    vals = _f32(vals)
+    nx, ny, nz = field.shape
+    call("rb_mesh_block_store", ptr(blocks), c_long(blocks.numel()), c_int(B), ptr(vals), c_long(vals.numel()), c_int(nx), c_int(ny),
+         c_int(nz), ptr(field), stream_ptr())
+
+
+def mesh_block_fill(blocks, B, vals, field):
+    assert blocks.dtype == torch.int32 and field.dtype == torch.float32 and field.is_contiguous()
+    vals = _f32(vals)
+    assert vals.numel() == blocks.numel()
+    nx, ny, nz = field.shape
+    call("rb_mesh_block_fill", ptr(blocks), c_long(blocks.numel()), c_int(B), ptr(vals), c_int(nx), c_int(ny), c_int(nz), ptr(field),
+         stream_ptr())
