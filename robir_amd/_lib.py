@@ -27,11 +27,15 @@ class RobirHipError(RuntimeError):
 LEGACY_PATH = os.path.join(_HERE, "librobir_hip_legacy.so")
 _legacy = None
 ABI_VERSION = 8
+TRAIN_PATH = os.path.join(_HERE, "librobir_hip_train.so")
+_train = None
+TRAIN_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
-    """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library) and -- legacy=True --
-    librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
+    """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library), librobir_hip_train.so (the
+    training-side kernels, csrc/train/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel generations,
+    csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j", jobs, "all" if legacy else "default"],
@@ -76,6 +80,35 @@ def legacy():
         if os.environ.get("ROBIR_SDF_RING_WAVES") in ("4", "8"):      # value rows of the split SDF net: csrc/sdf_ring8.hip | sdf_ring.hip
             _legacy.rb_sdf_ring_waves(int(os.environ["ROBIR_SDF_RING_WAVES"]))
     return _legacy
+
+
+def train():
+    """The training library (include/robir_hip_train.h; `make -C robir_amd/csrc train`): the reverse mode of the spec auto-encoder.  Its own
+    loader and its own error text -- a missing file is reported as such, never as a missing legacy entry point."""
+    global _train
+    if _train is None:
+        if not os.path.exists(TRAIN_PATH):
+            raise RobirHipError(f"{TRAIN_PATH} not found: the TRAINING library (material-network gradients, robir_amd/ae_autograd.py) is built "
+                                "by `python -c 'import __graft_entry__ as g; g.build()'` or `make -C robir_amd/csrc train` -- there is no "
+                                "PyTorch fallback for its kernels")
+        L = ctypes.CDLL(TRAIN_PATH)
+        L.rb_train_last_error.restype = ctypes.c_char_p
+        L.rb_train_ae_bwd_scratch_bytes.restype = ctypes.c_long
+        if L.rb_train_abi_version() != TRAIN_ABI_VERSION:
+            raise RobirHipError("librobir_hip_train.so ABI version mismatch")
+        _train = L
+    return _train
+
+
+def call_train(name, *args):
+    """An entry point of the training library (never resolved against the other two)."""
+    L = train()
+    fn = getattr(L, name, None)
+    if fn is None:
+        raise RobirHipError(f"{name} is not exported by librobir_hip_train.so")
+    rc = fn(*args)
+    if rc != 0:
+        raise RobirHipError(f"{name} failed ({rc}): {L.rb_train_last_error().decode()}")
 
 
 def legacy_loaded():

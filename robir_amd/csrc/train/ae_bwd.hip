@@ -1,0 +1,358 @@
+// librobir_hip_train.so: reverse mode of one SparseAE with smooth_on_latent=True (include/robir_hip_train.h).
+//
+// Everything is fp64: the layer activations are recomputed from the fp32 feature rows and the fp32 nn.Linear parameters, the three product
+// families (activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ) run on v_mfma_f64_16x16x4_f64 through ONE tiled kernel (k_gemm64)
+// whose operands are addressed by (row stride, column stride), and each stored gradient is rounded to fp32 once (k_finish).
+//
+// Reductions over rows: dW / db of a layer is a GEMM whose REDUCTION dimension is the slab's rows; one thread owns one element of the fp64
+// accumulator (no atomics, no split over rows), slabs are enqueued in order on one stream and add into that element in slab order.  The
+// accumulation order is therefore a function of (n, slab_rows) alone.
+//
+// The decoder's two passes (clean latent | latent + noise * scale) are stacked as 2 S rows of one problem: their weight gradients are one sum.
+#include <hip/hip_runtime.h>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include "../../../include/robir_hip_train.h"
+
+namespace {
+
+thread_local char g_err[512] = "";
+
+int fail(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return 1;
+}
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int BM = 64, BN = 64, BK = 16;      // block tile: four waves, wave w owns rows 16 w .. 16 w + 15 and all 64 columns (4 MFMA tiles)
+constexpr int LDS_LD = 80;                    // doubles per k-row of a tile in LDS: 160 dwords, consecutive k-rows start 32 banks apart
+constexpr double SLOPE = 0.2;                 // nn.LeakyReLU(0.2)
+
+enum { EPI_FWD = 0, EPI_BWD = 1, EPI_ACC = 2 };
+
+struct Gemm {
+    // C[m,n] = sum_k A(m,k) B(k,n);  A(m,k) = A[m sam + k sak], B(k,n) = B[k sbk + n sbn] (fp32 or fp64 elements), zero outside M x K / K x N
+    const void* A; long sam, sak; int a_f32;
+    const void* B; long sbk, sbn; int b_f32;
+    int ones_col;             // >= 0: B(k, ones_col) = 1 for every k < K and no memory is read for that column (db = dZ^T 1 rides along with dW)
+    int M, N, K;
+    int epi;
+    double* C; long ldc;
+    const float* bias;        // EPI_FWD: + bias[n]
+    int lrelu;                // EPI_FWD: LeakyReLU on the result.  EPI_BWD: result *= LeakyReLU'(mask[m,n]), mask = the stored activation
+    const double* mask; long ldm;
+    int first;                // EPI_ACC: 1 = store, 0 = add to what C holds (slab order)
+};
+
+__device__ __forceinline__ double ld_elem(const void* p, long i, int f32) {
+    return f32 ? (double)((const float*)p)[i] : ((const double*)p)[i];
+}
+
+__global__ __launch_bounds__(256) void k_gemm64(Gemm g) {
+    __shared__ double As[BK][LDS_LD];
+    __shared__ double Bs[BK][LDS_LD];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    double4_t acc[4];
+    for (int i = 0; i < 4; ++i) acc[i] = double4_t{0.0, 0.0, 0.0, 0.0};
+    const bool a_kfast = g.sak == 1, b_nfast = g.sbn == 1;
+    for (int k0 = 0; k0 < g.K; k0 += BK) {
+        for (int i = 0; i < 4; ++i) {
+            const int idx = t + 256 * i;
+            int m, k;
+            if (a_kfast) { k = idx & 15; m = idx >> 4; } else { m = idx & 63; k = idx >> 6; }
+            const int gm = m0 + m, gk = k0 + k;
+            As[k][m] = (gm < g.M && gk < g.K) ? ld_elem(g.A, (long)gm * g.sam + (long)gk * g.sak, g.a_f32) : 0.0;
+            int n;
+            if (b_nfast) { n = idx & 63; k = idx >> 6; } else { k = idx & 15; n = idx >> 4; }
+            const int gn = n0 + n;
+            const int gk2 = k0 + k;
+            double v = 0.0;
+            if (gn < g.N && gk2 < g.K) v = gn == g.ones_col ? 1.0 : ld_elem(g.B, (long)gk2 * g.sbk + (long)gn * g.sbn, g.b_f32);
+            Bs[k][n] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 4) {
+            // operand lane map of the 16x16x4 forms: lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]
+            const double a = As[kk + (lane >> 4)][16 * w + (lane & 15)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double b = Bs[kk + (lane >> 4)][16 * j + (lane & 15)];
+                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // C/D lane map of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 r  (NOT the f32 forms' 4 (lane >> 4) + r)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + 16 * j + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 16 * w + (lane >> 4) + 4 * r;
+            if (m >= g.M || n >= g.N) continue;
+            double v = acc[j][r];
+            double* c = g.C + (long)m * g.ldc + n;
+            if (g.epi == EPI_FWD) {
+                v += (double)g.bias[n];
+                if (g.lrelu) v = v > 0.0 ? v : SLOPE * v;
+                *c = v;
+            } else if (g.epi == EPI_BWD) {
+                // the stored activation has the sign of its pre-activation (slope > 0), and a(0) = 0 takes the slope like torch's leaky_relu
+                if (g.lrelu) v *= g.mask[(long)m * g.ldm + n] > 0.0 ? 1.0 : SLOPE;
+                *c = v;
+            } else {
+                *c = g.first ? v : *c + v;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ double sigmoid64(double x) { return 1.0 / (1.0 + exp(-x)); }
+
+// raw [S,32] (encoder output) -> E = raw (1 - var), LAT rows [0,S) = act(E), rows [S,2S) = act(E) + noise * scale
+__global__ void k_latent(const double* raw, const float* var, const float* noise, double scale, int act, long S, double* E, double* LAT) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * 32) return;
+    const int j = (int)(i & 31);
+    const double e = raw[i] * (1.0 - (var ? (double)var[j] : 0.0));
+    E[i] = e;
+    const double lat = act == 0 ? sigmoid64(e) : (e > 20.0 ? e : log1p(exp(e)));      // F.softplus: beta 1, threshold 20
+    LAT[i] = lat;
+    LAT[S * 32 + i] = lat + (noise ? (double)noise[i] * scale : 0.0);
+}
+
+// Z [2S,od] pre-activation outputs -> in place d loss / d Z = upstream * out_act'(Z); rows [0,S) take g_out, rows [S,2S) g_xi; NULL = zero
+__global__ void k_out_grad(double* Z, const float* g_out, const float* g_xi, int sig, long S, int od) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * S * od) return;
+    const bool second = i >= S * od;
+    const float* g = second ? g_xi : g_out;
+    double v = 0.0;
+    if (g) {
+        v = (double)g[second ? i - S * od : i];
+        if (sig) {
+            const double s = sigmoid64(Z[i]);
+            v *= s * (1.0 - s);
+        }
+    }
+    Z[i] = v;
+}
+
+// d LAT [2S,32] (both passes; NULL: no decoder contribution) + upstream on E -> d raw [S,32]
+__global__ void k_latent_grad(const double* dLAT, const double* E, const float* var, const float* g_raw, int act, long S, double* dRAW) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * 32) return;
+    const int j = (int)(i & 31);
+    const double e = E[i];
+    const double s = sigmoid64(e);
+    const double d = act == 0 ? s * (1.0 - s) : (e > 20.0 ? 1.0 : s);
+    double de = dLAT ? (dLAT[i] + dLAT[S * 32 + i]) * d : 0.0;
+    if (g_raw) de += (double)g_raw[i];
+    dRAW[i] = de * (1.0 - (var ? (double)var[j] : 0.0));
+}
+
+// fp64 accumulator [n_out, k_in + 1] (last column: bias) -> the parameter-shaped fp32 gradients, one rounding each
+__global__ void k_finish(const double* acc, int n_out, int k_in, float* gW, float* gb) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n_out * (k_in + 1)) return;
+    const int o = (int)(i / (k_in + 1)), c = (int)(i % (k_in + 1));
+    if (c < k_in) {
+        if (gW) gW[(long)o * k_in + c] = (float)acc[i];
+    } else if (gb) {
+        gb[o] = (float)acc[i];
+    }
+}
+
+struct Layer { int n_out, k_in; long in_ld; };      // in_ld: row stride of the layer's input rows
+
+struct Plan {
+    Layer L[8];
+    long acc_off[8];          // doubles
+    long acc_total;
+    // per-slab buffers, offsets in doubles (functions of S = slab rows and od)
+    long A[4], RAW, E, LAT, H[2], Z, dH[2], dLAT, dRAW, dZ[2], total;
+};
+
+Plan make_plan(long S, int in_dim, int od) {
+    Plan p;
+    const int no[8] = {512, 512, 512, 512, 32, 128, 128, od};
+    const int ki[8] = {in_dim, 512, 512, 512, 512, 32, 128, 128};
+    const long ld[8] = {64, 512, 512, 512, 512, 32, 128, 128};
+    long o = 0;
+    for (int l = 0; l < 8; ++l) {
+        p.L[l] = Layer{no[l], ki[l], ld[l]};
+        p.acc_off[l] = o;
+        o += (long)no[l] * (ki[l] + 1);
+    }
+    p.acc_total = o;
+    auto take = [&](long n) { long at = o; o += (n + 7) & ~7L; return at; };
+    for (int l = 0; l < 4; ++l) p.A[l] = take(S * 512);
+    p.RAW = take(S * 32);
+    p.E = take(S * 32);
+    p.LAT = take(2 * S * 32);
+    p.H[0] = take(2 * S * 128);
+    p.H[1] = take(2 * S * 128);
+    p.Z = take(2 * S * od);
+    p.dH[0] = take(2 * S * 128);
+    p.dH[1] = take(2 * S * 128);
+    p.dLAT = take(2 * S * 32);
+    p.dRAW = take(S * 32);
+    p.dZ[0] = take(S * 512);
+    p.dZ[1] = take(S * 512);
+    p.total = o;
+    return p;
+}
+
+bool check_dims(long n, long slab_rows, int in_dim, int out_dim) {
+    if (n < 0) return fail("n = %ld is negative", n), false;
+    if (slab_rows < 1 || slab_rows > (1L << 20)) return fail("slab_rows = %ld outside [1, 2^20]", slab_rows), false;
+    if (in_dim < 1 || in_dim > 64) return fail("in_dim = %d outside [1, 64]", in_dim), false;
+    if (out_dim < 1 || out_dim > 16) return fail("out_dim = %d outside [1, 16]", out_dim), false;
+    return true;
+}
+
+thread_local int g_launches;
+
+int launch_gemm(const Gemm& g, hipStream_t st) {
+    if (g.M <= 0 || g.N <= 0) return 0;
+    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM);
+    hipLaunchKernelGGL(k_gemm64, grid, dim3(256), 0, st, g);
+    ++g_launches;
+    return hipGetLastError() != hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rb_train_abi_version(void) { return RB_TRAIN_ABI_VERSION; }
+
+const char* rb_train_last_error(void) { return g_err; }
+
+long rb_train_ae_bwd_scratch_bytes(long n, long slab_rows, int in_dim, int out_dim) {
+    if (!check_dims(n, slab_rows, in_dim, out_dim)) return -1;
+    const long S = n < slab_rows ? (n > 0 ? n : 1) : slab_rows;
+    return make_plan(S, in_dim, out_dim).total * (long)sizeof(double);
+}
+
+int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, double noise_scale, const float* var, int latent_act, int out_act,
+                    int out_dim, const float* const* params, const float* g_out, const float* g_out_xi, const float* g_raw,
+                    float* const* grads, long slab_rows, void* scratch, long scratch_bytes, int* stats, rb_train_stream_t stream) {
+    if (!check_dims(n, slab_rows, in_dim, out_dim)) return 1;
+    if (latent_act != 0 && latent_act != 1) return fail("latent_act = %d: 0 (sigmoid) or 1 (softplus)", latent_act);
+    if (out_act != 0 && out_act != 1) return fail("out_act = %d: 0 (none) or 1 (sigmoid)", out_act);
+    if (!params || !grads) return fail("null pointer: params / grads (HOST arrays of 16 device pointers)");
+    if (stats) stats[0] = stats[1] = 0;
+    if (n == 0) return 0;
+    if (!X) return fail("null pointer: X");
+    for (int i = 0; i < 16; ++i)
+        if (!params[i]) return fail("null pointer: params[%d]", i);
+    bool any = false, enc = false;
+    int lowest = 8;                                   // first layer that wants a gradient: the data path stops there
+    for (int l = 7; l >= 0; --l)
+        if (grads[2 * l] || grads[2 * l + 1]) { any = true; lowest = l; }
+    enc = lowest < 5;
+    if (!any) return 0;
+    const long S0 = n < slab_rows ? n : slab_rows;
+    const Plan p = make_plan(S0, in_dim, out_dim);
+    if (!scratch) return fail("null pointer: scratch");
+    if ((uintptr_t)scratch % 8) return fail("scratch is not 8-byte aligned");
+    if (scratch_bytes < p.total * (long)sizeof(double))
+        return fail("scratch too small: %ld bytes given, %ld needed (rb_train_ae_bwd_scratch_bytes)", scratch_bytes, p.total * (long)sizeof(double));
+    hipStream_t st = (hipStream_t)stream;
+    double* D = (double*)scratch;
+    g_launches = 0;
+    int bad = 0;
+    auto ew_grid = [](long items) { return dim3((unsigned)((items + 255) / 256)); };
+    const bool want_layer[8] = {grads[0] || grads[1], grads[2] || grads[3], grads[4] || grads[5], grads[6] || grads[7],
+                                grads[8] || grads[9], grads[10] || grads[11], grads[12] || grads[13], grads[14] || grads[15]};
+
+    for (long row0 = 0; row0 < n; row0 += S0) {
+        const long S = n - row0 < S0 ? n - row0 : S0;
+        const int first = row0 == 0;
+        const float* Xs = X + row0 * 64;
+        // input rows of layer l (fp32 features for l = 0, fp64 activations after), M rows
+        const void* in[8] = {Xs, D + p.A[0], D + p.A[1], D + p.A[2], D + p.A[3], D + p.LAT, D + p.H[0], D + p.H[1]};
+        double* out[8] = {D + p.A[0], D + p.A[1], D + p.A[2], D + p.A[3], D + p.RAW, D + p.H[0], D + p.H[1], D + p.Z};
+        auto forward = [&](int l, long M) {
+            const Layer& L = p.L[l];
+            Gemm g{};
+            g.A = in[l]; g.sam = L.in_ld; g.sak = 1; g.a_f32 = l == 0;
+            g.B = params[2 * l]; g.sbk = 1; g.sbn = L.k_in; g.b_f32 = 1;
+            g.ones_col = -1;
+            g.M = (int)M; g.N = L.n_out; g.K = L.k_in;
+            g.epi = EPI_FWD; g.C = out[l]; g.ldc = L.n_out; g.bias = params[2 * l + 1];
+            g.lrelu = l != 4 && l != 7;
+            bad |= launch_gemm(g, st);
+        };
+        // d loss / d (pre-activation of layer l) sits in dz [M, n_out]: accumulate dW | db, and (to != NULL) hand the gradient to layer l - 1
+        auto backward = [&](int l, long M, const double* dz, double* to, bool mask_prev) {
+            const Layer& L = p.L[l];
+            if (want_layer[l]) {
+                Gemm g{};
+                g.A = dz; g.sam = 1; g.sak = L.n_out; g.a_f32 = 0;                 // A(m = neuron, k = row)
+                g.B = in[l]; g.sbk = L.in_ld; g.sbn = 1; g.b_f32 = l == 0;          // B(k = row, n = input column)
+                g.ones_col = L.k_in;
+                g.M = L.n_out; g.N = L.k_in + 1; g.K = (int)M;
+                g.epi = EPI_ACC; g.C = D + p.acc_off[l]; g.ldc = L.k_in + 1; g.first = first;
+                bad |= launch_gemm(g, st);
+            }
+            if (to) {
+                Gemm g{};
+                g.A = dz; g.sam = L.n_out; g.sak = 1; g.a_f32 = 0;
+                g.B = params[2 * l]; g.sbk = L.k_in; g.sbn = 1; g.b_f32 = 1;
+                g.ones_col = -1;
+                g.M = (int)M; g.N = L.k_in; g.K = L.n_out;
+                g.epi = EPI_BWD; g.C = to; g.ldc = L.k_in;
+                g.lrelu = mask_prev; g.mask = (const double*)in[l]; g.ldm = L.in_ld;
+                bad |= launch_gemm(g, st);
+            }
+        };
+        for (int l = 0; l < 5; ++l) forward(l, S);
+        hipLaunchKernelGGL(k_latent, ew_grid(S * 32), dim3(256), 0, st, D + p.RAW, var, noise ? noise + row0 * 32 : nullptr, noise_scale,
+                           latent_act, S, D + p.E, D + p.LAT);
+        ++g_launches;
+        const bool dec_grad = g_out || g_out_xi;      // without an upstream on either output the decoder's gradients are zero
+        if (lowest < 8 && (dec_grad || first)) {
+            // (a slab after the first adds nothing when there is no upstream; the first one must still store the zeros)
+            for (int l = 5; l < 8; ++l) forward(l, 2 * S);
+            hipLaunchKernelGGL(k_out_grad, ew_grid(2 * S * out_dim), dim3(256), 0, st, D + p.Z, g_out ? g_out + row0 * out_dim : nullptr,
+                               g_out_xi ? g_out_xi + row0 * out_dim : nullptr, out_act, S, out_dim);
+            ++g_launches;
+            backward(7, 2 * S, D + p.Z, lowest < 7 ? D + p.dH[1] : nullptr, true);
+            if (lowest < 7) backward(6, 2 * S, D + p.dH[1], lowest < 6 ? D + p.dH[0] : nullptr, true);
+            if (lowest < 6) backward(5, 2 * S, D + p.dH[0], enc ? D + p.dLAT : nullptr, false);
+        }
+        if (!enc) continue;                           // no encoder parameter wants a gradient: the backward stops at the latent
+        const bool through_decoder = dec_grad || first;
+        hipLaunchKernelGGL(k_latent_grad, ew_grid(S * 32), dim3(256), 0, st, through_decoder ? D + p.dLAT : nullptr, D + p.E, var,
+                           g_raw ? g_raw + row0 * 32 : nullptr, latent_act, S, D + p.dRAW);
+        ++g_launches;
+        const double* dz = D + p.dRAW;
+        for (int l = 4; l >= lowest; --l) {
+            double* to = l > lowest ? D + p.dZ[l & 1] : nullptr;
+            backward(l, S, dz, to, true);
+            dz = to;
+        }
+        if (stats) stats[1] = 1;
+    }
+    for (int l = 0; l < 8; ++l) {
+        if (!want_layer[l]) continue;
+        const Layer& L = p.L[l];
+        hipLaunchKernelGGL(k_finish, ew_grid((long)L.n_out * (L.k_in + 1)), dim3(256), 0, st, D + p.acc_off[l], L.n_out, L.k_in,
+                           grads[2 * l], grads[2 * l + 1]);
+        ++g_launches;
+    }
+    if (stats) stats[0] = g_launches;
+    if (bad || hipGetLastError() != hipSuccess) return fail("kernel launch failed");
+    return 0;
+}
+
+}  // extern "C"

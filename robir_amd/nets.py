@@ -6,11 +6,12 @@ model/sg_envmap_material.py:40-275 (SparseAE, EnvmapMaterialNetwork),
 model/neus_model.py:312-438,489-560,644-650,682-884 (SDFNetwork, RenderingNetwork, SingleVarianceNetwork,
 NeuSModel, ImplicitNetworkMy).
 
-Forward-only: the network kernels carry no autograd.  A forward pass of a module that is in training mode, with grad enabled and
+Forward-only unless opted in: the network kernels carry no autograd.  A forward pass of a module that is in training mode, with grad enabled and
 a parameter that requires grad, raises ForwardOnlyError (`forward_only_guard`; the drop-in is for inference /
 --plot_only rendering) instead of handing detached outputs to a loss.  Material NETWORKS therefore still train on
 the reference's modules; what IS differentiable on the HIP path is the SG shading of their outputs (robir_amd/sg_autograd.py,
-sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis).
+sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis) and -- after the explicit
+opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py).
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """
@@ -55,7 +56,10 @@ PRECISE_GRAD_SPLIT = os.environ.get("ROBIR_PRECISE_GRAD", "split") == "split"   
 
 def forward_only_guard(module):
     """The HIP kernels have no backward: a training-mode call that autograd would have to differentiate must not silently
-    return detached tensors (loss.backward() would then train only whatever still carries a graph)."""
+    return detached tensors (loss.backward() would then train only whatever still carries a graph).  A module marked by
+    robir_amd.training.enable_material_training has a backward and passes; its unmarked sub-networks still raise."""
+    if getattr(module, "_material_training", False):
+        return
     if module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise ForwardOnlyError(f"{type(module).__name__}: robir_amd kernels are forward-only -- call .eval(), wrap the call in "
                                "torch.no_grad(), or freeze the parameters (training stays on the reference's modules)")
@@ -237,6 +241,11 @@ class SparseAE(nn.Module):
         lat, lat2 = ops.ae_latent(self._encode_points(pts), self._var(pts.device), self._latent_act_code(), noise, 0.01)
         return ops.ae_decode(lat, dec, self.out_dim, sig_out), ops.ae_decode(lat2, dec, self.out_dim, sig_out)
 
+    def _trainable(self):
+        """Marked by robir_amd.training.enable_material_training, grad mode on, a parameter that requires grad: calls build a graph."""
+        return (getattr(self, "_material_training", False) and torch.is_grad_enabled()
+                and any(p.requires_grad for p in self.parameters()))
+
     def _latent_act_code(self):
         name = getattr(self.lc_act, "__name__", "")
         if name == "softplus":
@@ -281,7 +290,11 @@ class SparseAE(nn.Module):
         forward_only_guard(self)
         flat = values.reshape(-1, values.shape[-1]).float()
         X = torch.zeros(flat.shape[0], 64, device=flat.device)
-        X[:, :self.in_dim] = flat
+        X[:, :self.in_dim] = flat.detach()
+        if self._trainable():
+            from . import ae_autograd
+            ae_autograd.refuse_input_grad(values=values)
+            return ae_autograd.run_features(self, X)[2].reshape(list(values.shape[:-1]) + [self.latent_dim])
         raw, _ = ops.ae_latent(self._encode(X), self._var(flat.device), 2)
         return raw.reshape(list(values.shape[:-1]) + [self.latent_dim])
 
@@ -424,14 +437,37 @@ class EnvmapMaterialNetwork(nn.Module):
                   lambda: ops.normalize3(self.normal_decoder_layer.run_pass(ops.feat_ipe(pts, 1e-5, nz_n, 0.02)), 1e-4, 1)]
         if want_spec:
             thunks.append(lambda: self.spec_brdf_encoder_layer.run_points(pts, nz_s))
-        res = run_concurrently(thunks, n)
+        trainable = (getattr(self, "_material_training", False) and torch.is_grad_enabled()
+                     and any(p.requires_grad for p in self.parameters()))
+        if trainable:
+            # robir_amd.training: the spec auto-encoder carries a graph and runs on the caller's stream; the normal decoder has no backward
+            # (no stage-3 loss term reaches it) and runs without one
+            from . import ae_autograd
+            ae_autograd.refuse_input_grad(points=points)
+            with torch.no_grad():
+                res = run_concurrently(thunks[:2], n)
+            if want_spec:
+                ae = self.spec_brdf_encoder_layer
+                if ae._trainable():
+                    brdf, brdf_r, _ = ae_autograd.run_points(ae, pts, nz_s)
+                else:
+                    with torch.no_grad():
+                        brdf, brdf_r = ae.run_points(pts, nz_s)
+                if not train_spec:                # the reference's .detach() (model/sg_envmap_material.py:196)
+                    brdf, brdf_r = brdf.detach(), brdf_r.detach()
+                res = list(res) + [(brdf, brdf_r)]
+        else:
+            res = run_concurrently(thunks, n)
         normal_map, random_xi_normal = res[0], res[1]
         if want_spec:
             brdf, brdf_r = res[2]
         if train_norm:
             return {"sg_normal_map": normal_map, "random_xi_normal": random_xi_normal}
         lgtSGs = self.restrict_lobes_upper(self.lgtSGs) if self.upper_hemi else self.lgtSGs
-        alb, rough, metal, alb_r, rough_r, metal_r = ops.material_decode(brdf, brdf_r)
+        if trainable and (brdf.requires_grad or brdf_r.requires_grad):
+            alb, rough, metal, alb_r, rough_r, metal_r = ae_autograd.material_decode(brdf, brdf_r)
+        else:
+            alb, rough, metal, alb_r, rough_r, metal_r = ops.material_decode(brdf, brdf_r)
         return {
             "sg_lgtSGs": lgtSGs,
             "sg_specular_reflectance": self.specular_reflectance,

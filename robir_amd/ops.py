@@ -492,6 +492,45 @@ def ae_decode(lat, blob, n_out, sigmoid_out):
     return Y
 
 
+AE_PARAM_NAMES = tuple(f"brdf_encoder_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias")) \
+    + tuple(f"brdf_decoder_layer.{2 * i}.{w}" for i in range(3) for w in ("weight", "bias"))
+AE_SLAB_ROWS = 16384
+
+
+def ae_backward(X, params, g_out=None, g_out_xi=None, g_raw=None, noise=None, var=None, latent_act=0, sigmoid_out=True, in_dim=63,
+                out_dim=5, want=AE_PARAM_NAMES, slab_rows=None, noise_scale=0.01):
+    """Reverse mode of one latent-smoothed SparseAE (rb_train_ae_bwd, include/robir_hip_train.h): X [n,64] the feature rows the forward saw,
+    params = the sixteen nn.Linear tensors in AE_PARAM_NAMES order, the three upstream gradients (None = absent) on out / out_xi / the
+    pre-activation latent.  -> (dict name -> gradient in the parameter's own shape for the names in `want`, stats dict: kernels enqueued,
+    whether the encoder was differentiated, scratch bytes).  Allocates the wanted gradients and the scratch, nothing else."""
+    X = _f32(X)
+    n, dev = X.shape[0], X.device
+    assert X.dim() == 2 and X.shape[1] == 64 and len(params) == 16
+    params = [_f32(p.detach()) for p in params]
+    opt = lambda t, cols: None if t is None else _f32(t.detach()).reshape(n, cols)
+    g_out, g_out_xi, g_raw, noise = opt(g_out, out_dim), opt(g_out_xi, out_dim), opt(g_raw, 32), opt(noise, 32)
+    var = None if var is None else _f32(var.detach()).reshape(32)
+    unknown = set(want) - set(AE_PARAM_NAMES)
+    if unknown:
+        raise KeyError(f"ae_backward: no such parameter: {sorted(unknown)}")
+    alloc = torch.zeros if n == 0 else torch.empty           # n > 0: k_finish stores every element of every wanted gradient
+    out = {k: alloc(p.shape, dtype=torch.float32, device=dev) for k, p in zip(AE_PARAM_NAMES, params) if k in want}
+    slab = int(slab_rows or AE_SLAB_ROWS)
+    stats = (c_int * 2)(0, 0)
+    nbytes = 0
+    if n > 0 and out:
+        nbytes = int(_lib.train().rb_train_ae_bwd_scratch_bytes(c_long(n), c_long(slab), c_int(in_dim), c_int(out_dim)))
+        if nbytes < 0:
+            raise _lib.RobirHipError("rb_train_ae_bwd_scratch_bytes: " + _lib.train().rb_train_last_error().decode())
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        P = (ctypes.c_void_p * 16)(*[p.data_ptr() for p in params])
+        G = (ctypes.c_void_p * 16)(*[out[k].data_ptr() if k in out else None for k in AE_PARAM_NAMES])
+        _lib.call_train("rb_train_ae_bwd", ptr(X), c_long(n), c_int(in_dim), ptr(noise), ctypes.c_double(noise_scale), ptr(var),
+                        c_int(latent_act), c_int(1 if sigmoid_out else 0), c_int(out_dim), P, ptr(g_out), ptr(g_out_xi), ptr(g_raw), G,
+                        c_long(slab), ptr(scratch), c_long(nbytes), stats, stream_ptr())
+    return out, {"launches": int(stats[0]), "encoder_pass": bool(stats[1]), "scratch_bytes": nbytes}
+
+
 def axpy(a, b, s):
     a, b = _f32(a), _f32(b)
     y = torch.empty_like(a)
