@@ -15,14 +15,14 @@ opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of E
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """
-import math
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, packing
+from . import dispatch, ops, packing
+from .precision import cesr_precision, mlp_precision  # noqa: F401  ('f16x6' under the default policy, 'f16x3' under ROBIR_PRECISION=split)
 
 
 class _Packed:
@@ -34,17 +34,30 @@ class _Packed:
         self._cache = {}
         self._params = {}
 
-    def get(self, key, module, builder):
+    def blob(self, key, module, table, **more):
+        """The packed blob `key` of `module`: table[key] = (packing function by name -- looked up when it packs -- or a callable, state-dict
+        prefix, extra keyword arguments of the packer); more: keyword arguments known per instance only."""
         params = self._params.get(id(module))
         if params is None:
             params = self._params[id(module)] = list(module.parameters())
         sig = (tuple((p.data_ptr(), p._version) for p in params), params[0].device)
         ent = self._cache.get(key)
         if ent is None or ent[0] != sig:
-            sd = {k: v.detach() for k, v in module.state_dict(prefix="").items()}
-            ent = (sig, builder(sd))
-            self._cache[key] = ent
+            packer, prefix, kw = table[key]
+            fn = packer if callable(packer) else getattr(packing, packer)
+            sd = {prefix + k: v.detach() for k, v in module.state_dict(prefix="").items()}
+            ent = self._cache[key] = (sig, fn(sd, device=params[0].device, **kw, **more))
         return ent[1]
+
+
+def _blob_alias(key, sdf_only=None):
+    """The accessor names that tools and tests use: packed_*() is _blob(key), packed_*(full=False) of the SDF network _blob(sdf_only)."""
+    return lambda self, full=True: self._blob(key if full or sdf_only is None else sdf_only)
+
+
+def _h3(route):
+    """The scale_log2 argument of the split-precision kernels, for the routes that take one."""
+    return {"scale_log2": packing.H3_SCALE_LOG2} if route.scale_log2 else {}
 
 
 class ForwardOnlyError(RuntimeError):
@@ -70,10 +83,9 @@ def forward_only_guard(module):
 # latency (0.12 ms) on a machine with 256 CUs, and a chunk runs five of them back to back.  Independent nets of one forward
 # are therefore issued on side streams when the batch is small (joined before anything consumes them).  Whole-view batches
 # fill the GPU by themselves and stay on the caller's stream.
-import os as _os
-SIDE_STREAMS = _os.environ.get("ROBIR_SIDE_STREAMS", "1") != "0"
+SIDE_STREAMS = os.environ.get("ROBIR_SIDE_STREAMS", "1") != "0"
 SIDE_STREAM_MAX_ROWS = 8192
-BORROW_SLAB_ROWS = int(_os.environ.get("ROBIR_BORROW_SLAB_ROWS", "65536"))     # rays per borrow_color slab (NeuSRenderer.batch_borrow_color)
+BORROW_SLAB_ROWS = int(os.environ.get("ROBIR_BORROW_SLAB_ROWS", "65536"))     # rays per borrow_color slab (NeuSRenderer.batch_borrow_color)
 _SIDE_POOL = {}
 
 
@@ -108,14 +120,16 @@ def _require_dims(name, got, want):
         raise NotImplementedError(f"{name}: the HIP kernels are built for dims {want}, got {list(got)}")
 
 
-def _dev(module):
-    return next(module.parameters()).device
+def _mlp(dim, dims, n_out, act):
+    """nn.Sequential of Linear + act() per entry of dims and a last Linear to n_out (the reference's layer lists, same state-dict keys)."""
+    layers = []
+    for d in dims:
+        layers += [nn.Linear(dim, d), act()]
+        dim = d
+    return nn.Sequential(*layers, nn.Linear(dim, n_out))
 
 
 # ----------------------------------------------------------------------------------------- visibility
-from .precision import mlp_precision  # noqa: E402,F401  ('f16x6' under the default policy, 'f16x3' under ROBIR_PRECISION=split)
-
-
 class VisNetwork(nn.Module):
     """implicit_differentiable_renderer.py:225-258."""
 
@@ -124,47 +138,31 @@ class VisNetwork(nn.Module):
         if points_multires != 10 or dirs_multires != 10:
             raise NotImplementedError("HIP visibility kernels are built for points_multires = dirs_multires = 10")
         _require_dims("visibility_network", dims, [256] * 4)
-        layers, dim = [], 126
-        for d in dims:
-            layers += [nn.Linear(dim, d), nn.ReLU()]
-            dim = d
-        layers.append(nn.Linear(dim, 2))
-        self.vis_layer = nn.Sequential(*layers)
+        self.vis_layer = _mlp(126, dims, 2, nn.ReLU)
         self._packed = _Packed()
 
-    def _rename(self, sd):
-        return {"visibility_network." + k: v for k, v in sd.items()}
+    _BLOBS = {"full": ("pack_vis", "visibility_network.", {}), "full_h3": ("pack_vis_h3", "visibility_network.", {}),
+              "full_x6": ("pack_vis_x6", "visibility_network.", {}), "split": ("pack_vis_split", "visibility_network.", {})}
 
-    def packed_full(self):
-        return self._packed.get("full", self, lambda sd: packing.pack_vis(self._rename(sd), _dev(self)))
+    def _blob(self, key):
+        return self._packed.blob(key, self, self._BLOBS)
 
-    def packed_full_h3(self):
-        return self._packed.get("full_h3", self, lambda sd: packing.pack_vis_h3(self._rename(sd), _dev(self)))
-
-    def packed_full_x6(self):
-        return self._packed.get("full_x6", self, lambda sd: packing.pack_vis_x6(self._rename(sd), _dev(self)))
-
-    def packed_split(self):
-        return self._packed.get("split", self, lambda sd: packing.pack_vis_split(self._rename(sd), _dev(self)))
+    packed_full, packed_full_h3, packed_full_x6, packed_split = (_blob_alias(k) for k in ("full", "full_h3", "full_x6", "split"))
 
     def logits_from_features(self, X):
         """X [M,128] = [PE10(p) | PE10(d)] (ops.feat_vis) -> logits [M,2]; arithmetic per robir_amd.MLP_PRECISION."""
         forward_only_guard(self)
-        if mlp_precision() != "f16x3":          # feature rows: the f32-input MFMA kernel under 'fp32' and 'f16x6' alike
-            return ops.vis_mlp(X, self.packed_full())
-        return ops.vis_mlp_h3(X, self.packed_full_h3(), packing.H3_SCALE_LOG2)
+        r = dispatch.vis_mlp(mlp_precision(), ops.SDF_FUSED_PE, points=False)
+        return getattr(ops, r.fn)(X, self._blob(r.blob), **_h3(r))
 
     def logits_from_points(self, points, dirs, rep=1):
         """points [M/rep,3], dirs [M,3] (rep consecutive directions per point) -> logits [M,2]: [PE10(p) | PE10(d)] is encoded
-        inside the MLP kernel (no feature rows)."""
+        inside the MLP kernel (no feature rows) unless ROBIR_SDF_FUSED_PE=0."""
         forward_only_guard(self)
-        if not ops.SDF_FUSED_PE:
+        r = dispatch.vis_mlp(mlp_precision(), ops.SDF_FUSED_PE, points=True)
+        if r.encode:
             return self.logits_from_features(ops.feat_vis(points.float().contiguous(), dirs.float().contiguous(), rep=rep))
-        if mlp_precision() == "f16x6":      # exact three-piece operands (csrc/vis_x6.hip)
-            return ops.vis_x6_points(points, dirs, self.packed_full_x6(), rep)
-        if mlp_precision() != "f16x3":
-            return ops.vis_mlp_points(points, dirs, self.packed_full(), rep)
-        return ops.vis_mlp_points(points, dirs, self.packed_full_h3(), rep, packing.H3_SCALE_LOG2)
+        return getattr(ops, r.fn)(points, dirs, self._blob(r.blob), rep, **_h3(r))
 
     def forward(self, points, view_dirs):
         forward_only_guard(self)
@@ -181,18 +179,8 @@ class SparseAE(nn.Module):
         super().__init__()
         if latent_dim != 32 or in_dim > 64 or out_dim > 16:
             raise NotImplementedError("HIP SparseAE kernels: in_dim <= 64, latent 32, out_dim <= 16")
-        enc, dim = [], in_dim
-        for d in [512, 512, 512, 512]:
-            enc += [nn.Linear(dim, d), nn.LeakyReLU(0.2)]
-            dim = d
-        enc.append(nn.Linear(dim, latent_dim))
-        self.brdf_encoder_layer = nn.Sequential(*enc)
-        dec, dim = [], latent_dim
-        for d in [128, 128]:
-            dec += [nn.Linear(dim, d), nn.LeakyReLU(0.2)]
-            dim = d
-        dec.append(nn.Linear(dim, out_dim))
-        self.brdf_decoder_layer = nn.Sequential(*dec)
+        self.brdf_encoder_layer = _mlp(in_dim, [512] * 4, latent_dim, lambda: nn.LeakyReLU(0.2))
+        self.brdf_decoder_layer = _mlp(latent_dim, [128, 128], out_dim, lambda: nn.LeakyReLU(0.2))
         self.in_dim, self.out_dim, self.latent_dim = in_dim, out_dim, latent_dim
         self.smooth_on_latent = smooth_on_latent
         self.out_act = out_act
@@ -201,45 +189,40 @@ class SparseAE(nn.Module):
         self.var = torch.zeros(latent_dim)     # plain attribute, like the reference (not in the state dict)
         self._packed = _Packed()
 
+    _BLOBS = {"ae": ("pack_sparse_ae", "ae.", {"prefix": "ae"}), "enc_h3": ("pack_sparse_ae_encoder_h3", "ae.", {"prefix": "ae"}),
+              "enc_x6": ("pack_sparse_ae_encoder_x6", "ae.", {"prefix": "ae"})}
+
+    def _blob(self, key):
+        b = self._packed.blob(key, self, self._BLOBS)
+        return b[0] if key == "ae" else b          # pack_sparse_ae: (encoder, decoder)
+
     def _blobs(self):
-        return self._packed.get("ae", self, lambda sd: packing.pack_sparse_ae(
-            {"ae." + k: v for k, v in sd.items()}, "ae", _dev(self)))
+        return self._packed.blob("ae", self, self._BLOBS)
 
     def _encode(self, X):
-        if mlp_precision() == "f16x3":
-            blob = self._packed.get("enc_h3", self, lambda sd: packing.pack_sparse_ae_encoder_h3(
-                {"ae." + k: v for k, v in sd.items()}, "ae", _dev(self)))
-            return ops.wide_mlp_h3(X, blob, True, packing.H3_SCALE_LOG2)
-        if mlp_precision() == "f16x6":      # exact three-piece operands (csrc/wide_x6.hip)
-            blob = self._packed.get("enc_x6", self, lambda sd: packing.pack_sparse_ae_encoder_x6(
-                {"ae." + k: v for k, v in sd.items()}, "ae", _dev(self)))
-            return ops.wide_x6(X, blob, True)
-        return ops.ae_encode(X, self._blobs()[0])
+        r = dispatch.wide(mlp_precision(), ops.SDF_FUSED_PE, points=False, encoder=True)
+        return getattr(ops, r.fn)(X, self._blob(r.blob), *((True,) if r.flag else ()), **_h3(r))
 
     def _encode_points(self, pts):
-        """_encode(feat_pe10(pts)) with the encoding fused into the encoder kernel."""
-        if not ops.SDF_FUSED_PE:
+        """_encode(feat_pe10(pts)) with the encoding fused into the encoder kernel unless ROBIR_SDF_FUSED_PE=0."""
+        r = dispatch.wide(mlp_precision(), ops.SDF_FUSED_PE, points=True, encoder=True)
+        if r.encode:
             return self._encode(ops.feat_pe10(pts))
-        if mlp_precision() == "f16x3":
-            blob = self._packed.get("enc_h3", self, lambda sd: packing.pack_sparse_ae_encoder_h3(
-                {"ae." + k: v for k, v in sd.items()}, "ae", _dev(self)))
-            return ops.wide_mlp_points(pts, None, blob, True, packing.H3_SCALE_LOG2)
-        if mlp_precision() == "f16x6":      # exact three-piece operands (csrc/wide_x6.hip)
-            blob = self._packed.get("enc_x6", self, lambda sd: packing.pack_sparse_ae_encoder_x6(
-                {"ae." + k: v for k, v in sd.items()}, "ae", _dev(self)))
-            return ops.wide_x6_points(pts, None, blob, True)
-        return ops.wide_mlp_points(pts, None, self._blobs()[0], True)
+        return getattr(ops, r.fn)(pts, None, self._blob(r.blob), True, **_h3(r))
 
     def run_points(self, pts, noise):
         """run(feat_pe10(pts), noise=noise) for latent-smoothed auto-encoders, straight from the points."""
         forward_only_guard(self)
         assert self.smooth_on_latent
         enc, dec = self._blobs()
-        sig_out = self.out_act is not None
-        if sig_out and getattr(self.out_act, "__name__", "") != "sigmoid":
-            raise NotImplementedError("out_act must be torch.sigmoid or None")
+        sig_out = self._sigmoid_out()
         lat, lat2 = ops.ae_latent(self._encode_points(pts), self._var(pts.device), self._latent_act_code(), noise, 0.01)
         return ops.ae_decode(lat, dec, self.out_dim, sig_out), ops.ae_decode(lat2, dec, self.out_dim, sig_out)
+
+    def _sigmoid_out(self):
+        if self.out_act is not None and getattr(self.out_act, "__name__", "") != "sigmoid":
+            raise NotImplementedError("out_act must be torch.sigmoid or None")
+        return self.out_act is not None
 
     def _trainable(self):
         """Marked by robir_amd.training.enable_material_training, grad mode on, a parameter that requires grad: calls build a graph."""
@@ -266,9 +249,7 @@ class SparseAE(nn.Module):
         forward_only_guard(self)
         enc, dec = self._blobs()
         dev = X.device
-        sig_out = self.out_act is not None
-        if sig_out and getattr(self.out_act, "__name__", "") != "sigmoid":
-            raise NotImplementedError("out_act must be torch.sigmoid or None")
+        sig_out = self._sigmoid_out()
         if self.smooth_on_latent:
             lat, lat2 = ops.ae_latent(self._encode(X), self._var(dev), self._latent_act_code(), noise, 0.01)
         else:
@@ -335,22 +316,18 @@ class IndirctIllumNetwork(nn.Module):
         self.num_lgt_sgs = num_lgt_sgs
         self.use_hdr = not no_hdr              # hdr_mode == -1: no hdr-shift input column (feature 63 stays zero)
         in_dim = 64 if self.use_hdr else 63
-        layers, dim = [], in_dim
-        for d in dims:
-            layers += [nn.Linear(dim, d), nn.ReLU()]
-            dim = d
-        layers.append(nn.Linear(dim, num_lgt_sgs * 6))
-        self.lobe_layer = nn.Sequential(*layers)
+        self.lobe_layer = _mlp(in_dim, dims, num_lgt_sgs * 6, nn.ReLU)
         self.integral_layer = SparseAE(in_dim, 3, out_act=None, smooth_on_latent=False)
         self.integral_layer.lc_act = torch.nn.functional.softplus
         self._packed = _Packed()
+
+    _BLOBS = {"lobe": ("pack_illum", "indirect_illum_network.lobe_layer.", {}), "lobe_h3": ("pack_illum_h3", "indirect_illum_network.lobe_layer.", {}),
+              "lobe_x6": ("pack_illum_x6", "indirect_illum_network.lobe_layer.", {})}
 
     def forward(self, points, hdr_shift, noise=None):
         forward_only_guard(self)
         n = points.shape[0]
         dev = points.device
-        blob = self._packed.get("lobe", self.lobe_layer, lambda sd: packing.pack_illum(
-            {"indirect_illum_network.lobe_layer." + k: v for k, v in sd.items()}, dev))
         X = ops.feat_pe10(points.float().contiguous(), extra=hdr_shift.float().contiguous() if self.use_hdr else None)
         if noise is None:
             noise = torch.randn(n, 64, device=dev)
@@ -359,20 +336,12 @@ class IndirctIllumNetwork(nn.Module):
         noise = noise.float().contiguous()
 
         def lobes():
+            r = dispatch.wide(mlp_precision(), ops.SDF_FUSED_PE, points=True, encoder=False)
+            blob = self._packed.blob(r.blob, self.lobe_layer, self._BLOBS)
+            if r.encode:        # feature rows; else [PE10(x) | hdr_shift] encoded inside the lobe net's kernel
+                return ops.illum_decode(getattr(ops, r.fn)(X, blob, *((False,) if r.flag else ()), **_h3(r)))
             hdr = hdr_shift.float().contiguous() if self.use_hdr else None
-            if mlp_precision() == "f16x3":
-                blob3 = self._packed.get("lobe_h3", self.lobe_layer, lambda sd: packing.pack_illum_h3(
-                    {"indirect_illum_network.lobe_layer." + k: v for k, v in sd.items()}, dev))
-                if ops.SDF_FUSED_PE:        # [PE10(x) | hdr_shift] encoded inside the lobe net's kernel
-                    return ops.illum_decode(ops.wide_mlp_points(points, hdr, blob3, False, packing.H3_SCALE_LOG2))
-                return ops.illum_decode(ops.wide_mlp_h3(X, blob3, False, packing.H3_SCALE_LOG2))
-            if ops.SDF_FUSED_PE and mlp_precision() == "f16x6":      # exact three-piece operands (csrc/wide_x6.hip)
-                blob6 = self._packed.get("lobe_x6", self.lobe_layer, lambda sd: packing.pack_illum_x6(
-                    {"indirect_illum_network.lobe_layer." + k: v for k, v in sd.items()}, dev))
-                return ops.illum_decode(ops.wide_x6_points(points, hdr, blob6, False))
-            if ops.SDF_FUSED_PE:
-                return ops.illum_decode(ops.wide_mlp_points(points, hdr, blob, False))
-            return ops.illum_decode(ops.illum_mlp(X, blob))
+            return ops.illum_decode(getattr(ops, r.fn)(points, hdr, blob, False, **_h3(r)))
 
         def integral():       # only the perturbed pass is used (implicit_differentiable_renderer.py:220)
             return ops.abs_scale(self.integral_layer.run_pass(ops.axpy(X, noise, 0.02)), 1.0)
@@ -508,6 +477,12 @@ def _wn_linear(k_in, n_out):
     return nn.utils.weight_norm(nn.Linear(k_in, n_out))
 
 
+def _pack_sdf_back_x6(sd, device):
+    """ops.sdf_value_grad_x6's `back`: the one-tile kernel's transposed layers, the head row, the two-tile kernel's transposed layers."""
+    wt, w8 = packing.pack_sdf_back_x6(sd, device)
+    return wt, w8, packing.pack_sdf_back_x6(sd, device, two_tile=True)[0]
+
+
 class SDFNetwork(nn.Module):
     """neus_model.py:312-438.  Three shapes are compiled:
       (d_in 3,   d_out 257, 256 x 8, skip [4], multires 10)  -- the NeuS SDF network (default arguments)
@@ -534,113 +509,65 @@ class SDFNetwork(nn.Module):
         self.scale = 1
         self._packed = _Packed()
 
-    def _sd(self, sd):
-        return {"implicit_network.neus_model.sdf_network." + k: v for k, v in sd.items()}
+    _SDF = "implicit_network.neus_model.sdf_network."
+    _BLOBS = {"full": ("pack_sdf", _SDF, {"full": True}), "sdf": ("pack_sdf", _SDF, {"full": False}),
+              "full_h3": ("pack_sdf_h3", _SDF, {"full": True}), "sdf_h3": ("pack_sdf_h3", _SDF, {"full": False}),
+              "x6_full": ("pack_sdf_x6", _SDF, {"full": True}), "x6_dist": ("pack_sdf_x6", _SDF, {"full": False}),
+              "back": ("pack_sdf_back", _SDF, {}), "back_h3": ("pack_sdf_back_h3", _SDF, {}), "back_x6": (_pack_sdf_back_x6, _SDF, {})}
+    _BLOBS_512 = {"w512": ("pack_softplus512", "net.", {"prefix": "net."}), "w512_h3": ("pack_softplus512_h3", "net.", {"prefix": "net."}),
+                  "w512_x6": ("pack_softplus512_x6", "net.", {"prefix": "net."}), "w512_f16": ("pack_softplus512_f16", "net.", {"prefix": "net."})}
+
+    def _blob(self, key):
+        if self.kind == "neus":
+            return self._packed.blob(key, self, self._BLOBS)
+        return self._packed.blob(key, self, self._BLOBS_512, k_in=self.d_in)
 
     def packed(self, full=True):
-        if self.kind == "neus":
-            return self._packed.get("full" if full else "sdf", self,
-                                    lambda sd: packing.pack_sdf(self._sd(sd), _dev(self), full=full))
-        return self._packed.get("w512", self, lambda sd: packing.pack_softplus512(
-            {"net." + k: v for k, v in sd.items()}, "net.", self.d_in, _dev(self)))
+        return self._blob(("full" if full else "sdf") if self.kind == "neus" else "w512")
 
-    def packed_h3(self, full=True):
-        assert self.kind == "neus"
-        return self._packed.get("full_h3" if full else "sdf_h3", self,
-                                lambda sd: packing.pack_sdf_h3(self._sd(sd), _dev(self), full=full))
-
-    def packed_back_h3(self):
-        assert self.kind == "neus"
-        return self._packed.get("back_h3", self, lambda sd: packing.pack_sdf_back_h3(self._sd(sd), _dev(self)))
-
-    def packed_x6(self, full=True):
-        assert self.kind == "neus"
-        return self._packed.get("x6_full" if full else "x6_dist", self, lambda sd: packing.pack_sdf_x6(self._sd(sd), _dev(self), full=full))
-
-    def packed_back_x6(self):
-        assert self.kind == "neus"
-        def both(sd):
-            wt, w8 = packing.pack_sdf_back_x6(self._sd(sd), _dev(self))
-            return wt, w8, packing.pack_sdf_back_x6(self._sd(sd), _dev(self), two_tile=True)[0]
-        return self._packed.get("back_x6", self, both)
-
-    def packed_back(self):
-        assert self.kind == "neus"
-        return self._packed.get("back", self, lambda sd: packing.pack_sdf_back(self._sd(sd), _dev(self)))
+    packed_h3, packed_x6 = _blob_alias("full_h3", "sdf_h3"), _blob_alias("x6_full", "x6_dist")
+    packed_back, packed_back_h3, packed_back_x6, packed_w512_h3 = (_blob_alias(k) for k in ("back", "back_h3", "back_x6", "w512_h3"))
 
     def eval_points(self, x, in_scale=1.0, out_scale=1.0, full=True, grad=False, precise=False):
         """NeuS shape only.  x [M,3] -> (out [M,257] | [M], grad [M,3] | None); grad = d(out_scale*sdf(in_scale*x))/dx.
         precise: library-grade softplus (expf / log1pf on the f32-input MFMA, sdf-only modes) for VALUES that feed exact threshold
         decisions (the octree build).  With grad=True under the default policy the flag covers the value only: the gradient comes from
-        the exact-operand reverse pass (ROBIR_PRECISE_GRAD=split, the default), whose softplus is the hardware-transcendental form."""
+        the exact-operand reverse pass (ROBIR_PRECISE_GRAD=split, the default), whose softplus is the hardware-transcendental form.
+        The kernel(s) that serve the call: dispatch.sdf."""
         assert self.kind == "neus"
         forward_only_guard(self)
         x = x.float().contiguous()
         M = x.shape[0]
-        assert not (precise and full)
-        mode = (1 if full else 0) + (2 if grad else 0) + (4 if precise else 0)
-        if (mode == 3 and mlp_precision() == "f16x3" and ops.SDF_KERNEL == "ring" and ops.SDF_GRAD == "reverse"
-                and M >= ops.SDF_GRAD_MIN_POINTS):
-            # values once + one row vector back through the transposed layers, instead of three tangent rows per point
-            return ops.sdf_value_grad(x, M, self.packed_h3(True), self.packed_back_h3(), packing.H3_SCALE_LOG2, in_scale,
-                                      out_scale)
-        x6 = mlp_precision() == "f16x6"
-        if grad and precise and not full and x6 and ops.SDF_FUSED_PE and ops.SDF_GRAD == "reverse" and PRECISE_GRAD_SPLIT:
-            # the octree's cell table (octree_tracing.build): the VALUE with the library-grade softplus (one row per point on the f32-input
-            # MFMA), the GRADIENT by the policy's reverse pass on exact operands -- not three more tangent rows per point on the slow pipe
-            val = ops.sdf_mlp_points(x, M, self.packed(False), 4, in_scale, out_scale, out_scale * in_scale)[0]
-            return val, ops.sdf_value_grad_x6(x, M, self.packed_x6(True), self.packed_back_x6(), in_scale, out_scale)[1]
-        if (grad and not precise and mlp_precision() in ("fp32", "f16x6") and ops.SDF_FUSED_PE and ops.SDF_GRAD == "reverse"
-                and M >= (1 if x6 else ops.SDF_GRAD_F32_MIN_POINTS)):      # exact operands: three launches of 0.07 ms beat 0.31
-            # the same at the reference's precision: value pass on exact three-piece operands (or the f32-input MFMA) + one pass over
-            # the transposed layers on the f32-input MFMA
-            if x6:
-                out, g = ops.sdf_value_grad_x6(x, M, self.packed_x6(True), self.packed_back_x6(), in_scale, out_scale)
-            else:
-                out, g = ops.sdf_value_grad_f32(x, M, self.packed(True), self.packed_back(), in_scale, out_scale)
-            return (out if full else out[:, 0].contiguous()), g
-        if not grad and not precise and x6 and ops.SDF_FUSED_PE:
-            return ops.sdf_points_x6(x, M, self.packed_x6(full), full, in_scale, out_scale), None
-        if (not grad and not precise and mlp_precision() == "f16x3" and ops.SDF_KERNEL == "ring" and ops.SDF_FUSED_PE
-                and ops.sdf_ring_waves() == 8):
-            # value rows straight from the points: positional encoding fused into the network kernel (csrc/sdf_ring8.hip)
-            return ops.sdf_points_h3(x, M, self.packed_h3(full), full, packing.H3_SCALE_LOG2, in_scale, out_scale), None
-        if grad and not precise and mlp_precision() == "f16x3" and ops.SDF_KERNEL == "ring" and ops.SDF_FUSED_PE:
-            return ops.sdf_points_jvp_h3(x, M, self.packed_h3(full), full, packing.H3_SCALE_LOG2, in_scale, out_scale,
-                                         out_scale * in_scale)
-        if ops.SDF_FUSED_PE and (precise or mlp_precision() in ("fp32", "f16x6")):
-            # f32-input MFMA kernel with the encoding (tangent rows included) evaluated inside it
-            return ops.sdf_mlp_points(x, M, self.packed(full), mode, in_scale, out_scale, out_scale * in_scale)
-        X = ops.feat_pe10(x, scale=in_scale, jvp=grad)
-        if not precise and mlp_precision() == "f16x3":
-            return ops.sdf_mlp_h3(X, M, self.packed_h3(full), mode, packing.H3_SCALE_LOG2, out_scale, out_scale * in_scale)
-        return ops.sdf_mlp(X, M, self.packed(full), mode, out_scale, out_scale * in_scale)
+        route = dispatch.sdf(full, grad, precise, M, mlp_precision(), ops.SDF_FUSED_PE, ops.SDF_KERNEL, ops.SDF_GRAD, PRECISE_GRAD_SPLIT,
+                             ops.sdf_ring_waves, ops.SDF_GRAD_MIN_POINTS, ops.SDF_GRAD_F32_MIN_POINTS)
+        scale = {"i": in_scale, "o": out_scale, "g": out_scale * in_scale}
+        res = []
+        for c in route.calls:
+            args = [ops.feat_pe10(x, scale=in_scale, jvp=grad) if c.rows else x, M]
+            args += [self._packed.blob(k, self, self._BLOBS) for k in c.blobs]
+            args += c.sel
+            if c.scale_log2:
+                args.append(packing.H3_SCALE_LOG2)
+            res.append(getattr(ops, c.fn)(*args, *[scale[k] for k in c.scales]))
+        if route.combine == "precise":
+            return res[0][0], res[1][1]
+        if route.combine == "value":
+            return res[0], None
+        out, g = res[0]
+        return (out[:, 0].contiguous() if route.combine == "column" else out), g
 
-    def packed_w512_h3(self):
-        return self._packed.get("w512_h3", self, lambda sd: packing.pack_softplus512_h3(
-            {"net." + k: v for k, v in sd.items()}, "net.", self.d_in, _dev(self)))
+    def _cesr_route(self, r, x, M, kind, n_label):
+        return getattr(ops, r.fn)(x, M, kind, self._blob(r.blob), n_label=n_label, **_h3(r))
 
     def _cesr(self, X, M, kind, n_label=1):
         forward_only_guard(self)
-        if mlp_precision() == "f16x3":
-            return ops.cesr_net_h3(X, M, kind, self.packed_w512_h3(), packing.H3_SCALE_LOG2, n_label)
-        return ops.cesr_net(X, M, kind, self.packed(), n_label)
+        return self._cesr_route(dispatch.cesr(mlp_precision(), cesr_precision(), ops.SDF_FUSED_PE, points=False), X, M, kind, n_label)
 
     def _cesr_points(self, pts, M, kind, n_label=1):
-        """_cesr on PE10(pts) with the encoding evaluated inside the kernel (kind 0 normal_net, 2 shadow_net x labels)."""
+        """_cesr on PE10(pts) with the encoding evaluated inside the kernel (kind 0 normal_net, 2 shadow_net x labels), whatever
+        ROBIR_SDF_FUSED_PE says: a caller that honours it asks dispatch.cesr itself (renderer.CESRHook)."""
         forward_only_guard(self)
-        from .precision import cesr_precision
-        if cesr_precision() == "f16x1":     # plain f16, ONE product per multiply-add (csrc/cesr_f16.hip): the labelled throughput mode, NARROWER than fp32
-            blob = self._packed.get("w512_f16", self, lambda sd: packing.pack_softplus512_f16(
-                {"net." + k: v for k, v in sd.items()}, "net.", self.d_in, _dev(self)))
-            return ops.cesr_net_f16_points(pts, M, kind, blob, n_label)
-        if mlp_precision() == "f16x3":
-            return ops.cesr_net_points(pts, M, kind, self.packed_w512_h3(), n_label, packing.H3_SCALE_LOG2)
-        if mlp_precision() == "f16x6":      # exact three-piece operands (csrc/cesr_x6.hip)
-            blob = self._packed.get("w512_x6", self, lambda sd: packing.pack_softplus512_x6(
-                {"net." + k: v for k, v in sd.items()}, "net.", self.d_in, _dev(self)))
-            return ops.cesr_net_x6_points(pts, M, kind, blob, n_label)
-        return ops.cesr_net_points(pts, M, kind, self.packed(), n_label)
+        return self._cesr_route(dispatch.cesr(mlp_precision(), cesr_precision(), True, points=True), pts, M, kind, n_label)
 
     def eval_point_labels(self, Xp, n_label=128):
         """shadow_net on every (point, one-hot label) pair: Xp [n,64] PE10 features -> logits [n*n_label, 2]."""
@@ -693,35 +620,22 @@ class RenderingNetwork(nn.Module):
             setattr(self, "lin%d" % l, _wn_linear(dims[l], dims[l + 1]))
         self._packed = _Packed()
 
-    def packed(self):
-        return self._packed.get("c", self, lambda sd: packing.pack_color(
-            {"implicit_network.neus_model.color_network." + k: v for k, v in sd.items()}, _dev(self)))
+    _COL = "implicit_network.neus_model.color_network."
+    _BLOBS = {"c": ("pack_color", _COL, {}), "c_x6": ("pack_color_x6", _COL, {}), "c_h3": ("pack_color_h3", _COL, {})}
 
-    def packed_x6(self):
-        return self._packed.get("c_x6", self, lambda sd: packing.pack_color_x6(
-            {"implicit_network.neus_model.color_network." + k: v for k, v in sd.items()}, _dev(self)))
+    def _blob(self, key):
+        return self._packed.blob(key, self, self._BLOBS)
 
-    def packed_h3(self):
-        return self._packed.get("c_h3", self, lambda sd: packing.pack_color_h3(
-            {"implicit_network.neus_model.color_network." + k: v for k, v in sd.items()}, _dev(self)))
+    packed, packed_x6, packed_h3 = (_blob_alias(k) for k in ("c", "c_x6", "c_h3"))
 
     def forward(self, points, normals, view_dirs, feature_vectors, x_scale=1.0, feat_scale=1.0):
         forward_only_guard(self)
-        if mlp_precision() == "f16x3":
-            fn = ops.color_mlp_h3_points if ops.SDF_FUSED_PE else ops.color_mlp_h3_two      # encoding inside the kernel | tail rows
-            return fn(points, view_dirs, normals, feature_vectors, self.packed_h3(), packing.H3_SCALE_LOG2,
-                      x_scale=x_scale, feat_scale=feat_scale)
-        if ops.SDF_FUSED_PE and mlp_precision() == "f16x6":
-            return ops.color_x6_points(points, view_dirs, normals, feature_vectors, self.packed_x6(), x_scale=x_scale,
-                                       feat_scale=feat_scale)
-        if ops.SDF_FUSED_PE:
-            return ops.color_mlp_points(points, view_dirs, normals, feature_vectors, self.packed(), x_scale=x_scale,
-                                        feat_scale=feat_scale)
-        X = ops.feat_color(points.float().contiguous(), view_dirs.float().contiguous(), normals.float().contiguous(),
-                           feature_vectors, x_scale=x_scale, feat_scale=feat_scale)
-        if mlp_precision() == "f16x3":
-            return ops.color_mlp_h3(X, self.packed_h3(), packing.H3_SCALE_LOG2)
-        return ops.color_mlp(X, self.packed())
+        r = dispatch.color(mlp_precision(), ops.SDF_FUSED_PE)
+        if r.encode:
+            X = ops.feat_color(points.float().contiguous(), view_dirs.float().contiguous(), normals.float().contiguous(),
+                               feature_vectors, x_scale=x_scale, feat_scale=feat_scale)
+            return getattr(ops, r.fn)(X, self._blob(r.blob))
+        return getattr(ops, r.fn)(points, view_dirs, normals, feature_vectors, self._blob(r.blob), **_h3(r), x_scale=x_scale, feat_scale=feat_scale)
 
 
 class SingleVarianceNetwork(nn.Module):

@@ -1,11 +1,12 @@
 """Thin Python bindings over the C-ABI (include/robir_hip.h): allocate outputs with torch, pass raw pointers,
 sizes and the current HIP stream.  No arithmetic happens here."""
 import ctypes
+import functools
 import os
 
 import torch
 
-from . import _lib
+from . import _lib, dispatch
 from ._lib import ptr, stream_ptr, call
 
 c_long, c_int, c_float = ctypes.c_long, ctypes.c_int, ctypes.c_float
@@ -79,32 +80,27 @@ def feat_color(x, view, normal, feat, x_scale=1.0, feat_scale=1.0):
     return X
 
 
+def _color_args(x, view, normal, feat):
+    """Checked inputs of the colour kernels that read the feature columns in place, the row count and the rgb output."""
+    assert feat.dtype == torch.float32 and feat.stride(-1) == 1
+    return _f32(x), _f32(view), _f32(normal), x.shape[0], torch.empty(x.shape[0], 3, dtype=torch.float32, device=x.device)
+
+
 def color_mlp_h3_two(x, view, normal, feat, blob, scale_log2, x_scale=1.0, feat_scale=1.0):
     """feat_color + color_mlp_h3 without the assembled [M,304] rows: the 256 feature columns are read where they are."""
-    x, view, normal = _f32(x), _f32(view), _f32(normal)
-    assert feat.dtype == torch.float32 and feat.stride(-1) == 1
-    M = x.shape[0]
+    x, view, normal, M, rgb = _color_args(x, view, normal, feat)
     tail = torch.empty(M, 48, dtype=torch.float32, device=x.device)
-    rgb = torch.empty(M, 3, dtype=torch.float32, device=x.device)
     call("rb_feat_color_tail", ptr(x), c_float(x_scale), ptr(view), ptr(normal), c_long(M), ptr(tail), stream_ptr())
     call("rb_color_mlp_h3_two", ctypes.c_void_p(feat.data_ptr()), c_long(feat.stride(0)), c_float(feat_scale), ptr(tail), c_long(M),
          ptr(blob), c_int(scale_log2), ptr(rgb), stream_ptr())
     return rgb
 
 
-COLOR_RING_MIN_ROWS = 1           # the chunk-stream kernel wins at every size (one round: 0.040 vs 0.061 ms); 0 rows never launch
-
-
 def color_mlp_h3_points(x, view, normal, feat, blob, scale_log2, x_scale=1.0, feat_scale=1.0, ring=None):
     """The colour net with its encoding fused: feature columns read in place, [x | PE4(view) | normal] encoded inside the kernel.
-    ring (default: by batch size): the eight-wave chunk-stream kernel (csrc/color_ring8.hip) -- bit-identical rgb."""
-    x, view, normal = _f32(x), _f32(view), _f32(normal)
-    assert feat.dtype == torch.float32 and feat.stride(-1) == 1
-    M = x.shape[0]
-    rgb = torch.empty(M, 3, dtype=torch.float32, device=x.device)
-    if ring is None:
-        ring = M >= COLOR_RING_MIN_ROWS
-    if ring:
+    ring (the default: 0.040 vs 0.061 ms for one round): the eight-wave chunk-stream kernel (csrc/color_ring8.hip) -- bit-identical rgb."""
+    x, view, normal, M, rgb = _color_args(x, view, normal, feat)
+    if ring is None or ring:
         call("rb_color_ring_points", ctypes.c_void_p(feat.data_ptr()), c_long(feat.stride(0)), c_float(feat_scale), ptr(x),
              c_float(x_scale), ptr(view), ptr(normal), c_long(M), ptr(blob), c_int(scale_log2), ptr(rgb), c_int(0), stream_ptr())
         return rgb
@@ -180,22 +176,17 @@ def linear_pe10_256(x, blob):
     return Y
 
 
-WIDE_RING_MIN_ROWS = 1            # the chunk-stream kernels win at every size (one round of 64 rows: 0.067 vs 0.127 ms)
-
-
 def wide_mlp_points(x, extra, blob, encoder, scale_log2=None, ring=None):
     """512-wide nets on [PE10(x) | extra] with the encoding fused: encoder=False -> raw SG outputs [M,144], True -> raw latent [M,32];
-    scale_log2 None = f32-input MFMA kernel, else split precision; ring (split precision; default: by batch size): the chunk-stream
-    kernel (csrc/wide_ring.h) -- bit-identical outputs."""
+    scale_log2 None = f32-input MFMA kernel, else split precision; ring (split precision; the default: it wins at every size, one round
+    of 64 rows 0.067 vs 0.127 ms): the chunk-stream kernel (csrc/wide_ring.h) -- bit-identical outputs."""
     x = _f32(x)
     M = x.shape[0]
     e = _f32(extra).reshape(-1) if extra is not None else None
     Y = torch.empty(M, 32 if encoder else 144, dtype=torch.float32, device=x.device)
-    if ring is None:
-        ring = M >= WIDE_RING_MIN_ROWS
     if scale_log2 is None:
         call("rb_wide_mlp_points", ptr(x), ptr(e), c_long(M), ptr(blob), c_int(1 if encoder else 0), ptr(Y), stream_ptr())
-    elif ring:
+    elif ring is None or ring:
         call("rb_wide_mlp_ring_points", ptr(x), ptr(e), c_long(M), ptr(blob), c_int(1 if encoder else 0), c_int(scale_log2), ptr(Y),
              c_int(0), stream_ptr())
     else:
@@ -233,10 +224,7 @@ def sdf_mlp_points(x, M, blob, mode, in_scale=1.0, out_scale=1.0, grad_scale=1.0
 
 def color_mlp_points(x, view, normal, feat, blob, x_scale=1.0, feat_scale=1.0):
     """rb_color_mlp (f32-input MFMA) with the feature columns read in place and [x | PE4(view) | normal] encoded in the kernel."""
-    x, view, normal = _f32(x), _f32(view), _f32(normal)
-    assert feat.dtype == torch.float32 and feat.stride(-1) == 1
-    M = x.shape[0]
-    rgb = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+    x, view, normal, M, rgb = _color_args(x, view, normal, feat)
     call("rb_color_mlp_points", ctypes.c_void_p(feat.data_ptr()), c_long(feat.stride(0)), c_float(feat_scale), ptr(x), c_float(x_scale),
          ptr(view), ptr(normal), c_long(M), ptr(blob), ptr(rgb), stream_ptr())
     return rgb
@@ -245,10 +233,7 @@ def color_mlp_points(x, view, normal, feat, blob, x_scale=1.0, feat_scale=1.0):
 def color_x6_points(x, view, normal, feat, blob, x_scale=1.0, feat_scale=1.0, two_tile=None):
     """color_mlp_points on exact three-piece operands (blob = packing.pack_color_x6): csrc/color_x6t.hip (two tiles per wave, rounds of 128
     rows) from SDF_TWO_TILE_MIN_ROWS rows on, csrc/color_x6.hip (one tile, rounds of 64) below; two_tile forces either."""
-    x, view, normal = _f32(x), _f32(view), _f32(normal)
-    assert feat.dtype == torch.float32 and feat.stride(-1) == 1
-    M = x.shape[0]
-    rgb = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+    x, view, normal, M, rgb = _color_args(x, view, normal, feat)
     if two_tile is None:
         two_tile = sdf_two_tile(M)
     call("rb_color_x6_points", ctypes.c_void_p(feat.data_ptr()), c_long(feat.stride(0)), c_float(feat_scale), ptr(x), c_float(x_scale),
@@ -256,8 +241,7 @@ def color_x6_points(x, view, normal, feat, blob, x_scale=1.0, feat_scale=1.0, tw
     return rgb
 
 
-import os as _os
-SDF_KERNEL = _os.environ.get("ROBIR_SDF_KERNEL", "ring")     # "ring" | "v1" (first-generation k_sdf_mlp_h3)
+SDF_KERNEL = os.environ.get("ROBIR_SDF_KERNEL", "ring")     # "ring" | "v1" (first-generation k_sdf_mlp_h3)
 
 
 def sdf_mlp_h3(X, M, blob, mode, scale_log2, out_scale=1.0, grad_scale=1.0):
@@ -273,7 +257,7 @@ def sdf_mlp_h3(X, M, blob, mode, scale_log2, out_scale=1.0, grad_scale=1.0):
     return out0, grad
 
 
-SDF_FUSED_PE = _os.environ.get("ROBIR_SDF_FUSED_PE", "1") == "1"   # value rows / value+gradient straight from the points (csrc/sdf_ring8.hip)
+SDF_FUSED_PE = os.environ.get("ROBIR_SDF_FUSED_PE", "1") == "1"   # value rows / value+gradient straight from the points (csrc/sdf_ring8.hip)
 
 
 def sdf_points_h3(x, M, blob, full, scale_log2, in_scale=1.0, out_scale=1.0):
@@ -296,7 +280,7 @@ def sdf_points_jvp_h3(x, M, blob, full, scale_log2, in_scale=1.0, out_scale=1.0,
     return out0, grad
 
 
-SDF_GRAD = _os.environ.get("ROBIR_SDF_GRAD", "reverse")     # "reverse" (csrc/sdf_back.hip) | "forward" (mode 3 rows)
+SDF_GRAD = os.environ.get("ROBIR_SDF_GRAD", "reverse")     # "reverse" (csrc/sdf_back.hip) | "forward" (mode 3 rows)
 SDF_GRAD_MIN_POINTS = 16384       # below this the three-launch reverse form does not pay (0.25 ms floor; measured crossover)
 SDF_GRAD_F32_MIN_POINTS = 16384   # ... of the f32-input-MFMA form (three launches against one of the four-row forward-mode kernel)
 SDF_GRAD_SLAB = 1 << 20           # points per slab of the reverse form (8.5 KB of scratch per point)
@@ -313,64 +297,58 @@ def sdf_ring_waves():
     return int(_lib.legacy().rb_sdf_ring_waves(0))
 
 
-def sdf_value_grad(x, M, blob, back, scale_log2, in_scale=1.0, out_scale=1.0):
-    """All 257 outputs + d sdf / dx by the reverse-mode pass: x [M,3] -> out [M,257], grad [M,3]."""
-    wb, w8 = back
+def _sdf_value_grad_slabs(x, M, scratch_floats, key, launch):
+    """The frame the reverse-mode SDF forms share: out [M,257], grad [M,3], the cached per-(device, stream) scratch (entry `key`, sized by
+    scratch_floats(points of a slab)) and launch(x, n, out, grad, scratch) on each slab of SDF_GRAD_SLAB points."""
     out0 = torch.empty(M, 257, dtype=torch.float32, device=x.device)
     grad = torch.empty(M, 3, dtype=torch.float32, device=x.device)
     if M == 0:
         return out0, grad
     slab = min(M, SDF_GRAD_SLAB)
-    need = int(_lib.legacy().rb_sdf_value_grad_scratch_floats(c_long(slab)))
-    key = (x.device, torch.cuda.current_stream().cuda_stream)
+    need = int(scratch_floats(c_long(slab)))
+    key = (x.device, torch.cuda.current_stream().cuda_stream) + key
     scratch = _sdf_grad_scratch.get(key)
     if scratch is None or scratch.numel() < need:
         scratch = _sdf_grad_scratch[key] = torch.empty(need, dtype=torch.float32, device=x.device)
     x = _f32(x)
-    fused = SDF_FUSED_PE and sdf_ring_waves() == 8      # the encoding is fused into the eight-wave kernel
     for a in range(0, M, slab):
         n = min(slab, M - a)
-        if fused:
-            call("rb_sdf_value_grad_points", ptr(x[a:a + n]), c_long(n), c_float(in_scale), ptr(blob), ptr(wb), ptr(w8),
-                 c_int(scale_log2), c_float(out_scale), c_float(out_scale * in_scale), ptr(out0[a:a + n]), ptr(grad[a:a + n]),
-                 ptr(scratch), c_int(0), stream_ptr())
-        else:
-            X = feat_pe10(x[a:a + n], scale=in_scale)
-            call("rb_sdf_value_grad", ptr(X), c_long(n), ptr(blob), ptr(wb), ptr(w8), c_int(scale_log2), c_float(out_scale),
-                 c_float(out_scale * in_scale), ptr(out0[a:a + n]), ptr(grad[a:a + n]), ptr(scratch), c_int(0), stream_ptr())
+        launch(x[a:a + n], n, out0[a:a + n], grad[a:a + n], scratch)
     return out0, grad
+
+
+def sdf_value_grad(x, M, blob, back, scale_log2, in_scale=1.0, out_scale=1.0):
+    """All 257 outputs + d sdf / dx by the reverse-mode pass: x [M,3] -> out [M,257], grad [M,3]."""
+    wb, w8 = back
+
+    def launch(x, n, out0, grad, scratch):
+        if SDF_FUSED_PE and sdf_ring_waves() == 8:      # the encoding is fused into the eight-wave kernel
+            call("rb_sdf_value_grad_points", ptr(x), c_long(n), c_float(in_scale), ptr(blob), ptr(wb), ptr(w8), c_int(scale_log2),
+                 c_float(out_scale), c_float(out_scale * in_scale), ptr(out0), ptr(grad), ptr(scratch), c_int(0), stream_ptr())
+        else:
+            X = feat_pe10(x, scale=in_scale)
+            call("rb_sdf_value_grad", ptr(X), c_long(n), ptr(blob), ptr(wb), ptr(w8), c_int(scale_log2), c_float(out_scale),
+                 c_float(out_scale * in_scale), ptr(out0), ptr(grad), ptr(scratch), c_int(0), stream_ptr())
+    return _sdf_value_grad_slabs(x, M, lambda n: _lib.legacy().rb_sdf_value_grad_scratch_floats(n), (), launch)
 
 
 def sdf_value_grad_f32(x, M, blob, back, in_scale=1.0, out_scale=1.0):
     """sdf_value_grad at the reference's precision (f32-input MFMA; csrc/mlp_kernels.hip k_sdf_mlp<5> + k_sdf_back_f32): x [M,3] ->
     out [M,257], grad [M,3].  blob = packing.pack_sdf(full=True), back = packing.pack_sdf_back."""
     wt, w8 = back
-    out0 = torch.empty(M, 257, dtype=torch.float32, device=x.device)
-    grad = torch.empty(M, 3, dtype=torch.float32, device=x.device)
-    if M == 0:
-        return out0, grad
-    slab = min(M, SDF_GRAD_SLAB)
-    need = int(_lib.lib().rb_sdf_value_grad_f32_scratch_floats(c_long(slab)))
-    key = (x.device, torch.cuda.current_stream().cuda_stream, "f32")
-    scratch = _sdf_grad_scratch.get(key)
-    if scratch is None or scratch.numel() < need:
-        scratch = _sdf_grad_scratch[key] = torch.empty(need, dtype=torch.float32, device=x.device)
-    x = _f32(x)
-    for a in range(0, M, slab):
-        n = min(slab, M - a)
-        call("rb_sdf_value_grad_f32_points", ptr(x[a:a + n]), c_long(n), c_float(in_scale), ptr(blob), ptr(wt), ptr(w8),
-             c_float(out_scale), c_float(out_scale * in_scale), ptr(out0[a:a + n]), ptr(grad[a:a + n]), ptr(scratch), stream_ptr())
-    return out0, grad
+
+    def launch(x, n, out0, grad, scratch):
+        call("rb_sdf_value_grad_f32_points", ptr(x), c_long(n), c_float(in_scale), ptr(blob), ptr(wt), ptr(w8), c_float(out_scale),
+             c_float(out_scale * in_scale), ptr(out0), ptr(grad), ptr(scratch), stream_ptr())
+    return _sdf_value_grad_slabs(x, M, lambda n: _lib.lib().rb_sdf_value_grad_f32_scratch_floats(n), ("f32",), launch)
 
 
 SDF_TWO_TILE_MIN_ROWS = int(os.environ.get("ROBIR_SDF_TWO_TILE_MIN_ROWS", "16385"))
-_CU_COUNT = []
 
 
+@functools.lru_cache(None)
 def _compute_units():
-    if not _CU_COUNT:
-        _CU_COUNT.append(torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count if torch.cuda.is_available() else 256)
-    return _CU_COUNT[0]
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count if torch.cuda.is_available() else 256
 
 
 def sdf_two_tile(M):
@@ -406,24 +384,13 @@ def sdf_value_grad_x6(x, M, blob, back, in_scale=1.0, out_scale=1.0):
     head row, the two-tile kernel's transposed layers; a 2-tuple (round 3's form) runs the one-tile kernels at every size)."""
     wt, w8 = back[0], back[1]
     wt2 = back[2] if len(back) > 2 else None
-    out0 = torch.empty(M, 257, dtype=torch.float32, device=x.device)
-    grad = torch.empty(M, 3, dtype=torch.float32, device=x.device)
-    if M == 0:
-        return out0, grad
-    slab = min(M, SDF_GRAD_SLAB)
-    need = int(_lib.lib().rb_sdf_value_grad_f32_scratch_floats(c_long(slab)))
-    key = (x.device, torch.cuda.current_stream().cuda_stream, "f32")
-    scratch = _sdf_grad_scratch.get(key)
-    if scratch is None or scratch.numel() < need:
-        scratch = _sdf_grad_scratch[key] = torch.empty(need, dtype=torch.float32, device=x.device)
-    x = _f32(x)
-    for a in range(0, M, slab):
-        n = min(slab, M - a)
+
+    def launch(x, n, out0, grad, scratch):
         two = wt2 is not None and sdf_two_tile(n)
-        call("rb_sdf_value_grad_x6_points", ptr(x[a:a + n]), c_long(n), c_float(in_scale), ptr(blob), ptr(wt2 if two else wt), ptr(w8),
-             c_float(out_scale), c_float(out_scale * in_scale), ptr(out0[a:a + n]), ptr(grad[a:a + n]), ptr(scratch), c_int(1 if two else 0),
-             stream_ptr())
-    return out0, grad
+        call("rb_sdf_value_grad_x6_points", ptr(x), c_long(n), c_float(in_scale), ptr(blob), ptr(wt2 if two else wt), ptr(w8), c_float(out_scale),
+             c_float(out_scale * in_scale), ptr(out0), ptr(grad), ptr(scratch), c_int(1 if two else 0), stream_ptr())
+    # the same scratch entry as sdf_value_grad_f32: the two never run at once on a stream
+    return _sdf_value_grad_slabs(x, M, lambda n: _lib.lib().rb_sdf_value_grad_f32_scratch_floats(n), ("f32",), launch)
 
 
 def color_mlp(X, blob):
@@ -449,12 +416,10 @@ def illum_mlp(X, blob):
 
 def wide_mlp_h3(X, blob, encoder, scale_log2, ring=None):
     """Split-precision 512-wide nets on feature rows: encoder=False -> raw SG outputs [M,144]; encoder=True -> raw latent [M,32].
-    ring (default: by batch size): the chunk-stream kernel (csrc/wide_ring.h) -- bit-identical outputs."""
+    ring (the default): the chunk-stream kernel (csrc/wide_ring.h) -- bit-identical outputs."""
     M = X.shape[0]
     Y = torch.empty(M, 32 if encoder else 144, dtype=torch.float32, device=X.device)
-    if ring is None:
-        ring = M >= WIDE_RING_MIN_ROWS
-    if ring:
+    if ring is None or ring:
         call("rb_wide_mlp_ring", ptr(X), c_long(M), ptr(blob), c_int(1 if encoder else 0), c_int(scale_log2), ptr(Y), c_int(0), stream_ptr())
     else:
         call("rb_wide_mlp_h3", ptr(X), c_long(M), ptr(blob), c_int(1 if encoder else 0), c_int(scale_log2), ptr(Y), stream_ptr())
@@ -590,107 +555,61 @@ DVIS_X6_FORM = os.environ.get("ROBIR_DVIS_X6_FORM", "auto")          # what "f16
 def dvis_fused(normals, chunk_id, A, Bd, dirs, wdir, wsum, split, L, nsamp, argmax_vis=False, eval_count=None,
                precision="fp32"):
     """precision: 'fp32' (f32-input MFMA, exact fp32 fma chain), 'f16x6' (exact fp32 operands as three halves each, six f16
-    MFMA products per multiply-add: not narrower than fp32) or 'f16x3*' (split precision, 22-bit operands, ~2^-22 relative)."""
+    MFMA products per multiply-add: not narrower than fp32), 'f16x3*' (split precision, 22-bit operands, ~2^-22 relative) or 'f16x1' (plain
+    f16: NARROWER than fp32).  Which kernel form, weight blob and format serve the call: dispatch.dvis."""
     normals = _f32(normals)
-    if precision == "f16x3-auto":
-        # same arithmetic, bit-identical results: the streaming family balances small launches (a single 1024-pixel chunk) over
-        # the CUs; at whole-view sizes the one-point-per-workgroup kernel is as fast and needs no scratch
-        # (the tile-list forms cut a point's L*nsamp directions into whole 16-sample tiles: other shapes take the per-point kernel)
-        precision = "f16x3-v3" if normals.shape[0] <= DVIS_STREAM_MAX_POINTS and (L * nsamp) % 16 == 0 else "f16x3-v2"
-    h3 = precision.startswith("f16x3")
-    X6 = ("f16x6", "f16x6-1t", "f16x6-pt", "f16x6-stream")
-    assert h3 or precision in ("fp32", "f16x1") or precision in X6, precision
-    if precision == "f16x6":
-        # "auto": the persistent tile-list form for launches up to DVIS_STREAM_MAX_POINTS points (a single 1024-pixel chunk: balanced
-        # over the CUs, 0.4 % tile padding), one workgroup per point beyond (no scratch); the two are bit-identical
-        # (same bits); a light whose L*nsamp is not a multiple of 16 (odd lobe counts with nsamp = 8) cannot be cut into whole tiles of
-        # the global list and takes the per-point form at every size
-        # ... and at EVERY size for short direction lists (L * nsamp <= 1024: the CESR hook's nsamp = 8): a point then has four rounds of
-        # 128 pairs, the per-point prologue / half-empty last round weigh 5-6 % (tools/ab_dvis_forms.py, 8 / 32 / 128 chunks: 0.94-0.95 of
-        # the per-point form's time; with 4096 directions 0.99-1.00 -- there the per-point form stays: one launch, no 10 GB of scratch)
-        stream_ok = (L * nsamp) % 16 == 0 and (normals.shape[0] <= DVIS_STREAM_MAX_POINTS or L * nsamp <= DVIS_STREAM_SHORT_LIST)
-        precision = DVIS_X6_FORM if DVIS_X6_FORM != "auto" else ("f16x6-stream" if stream_ok else "f16x6-pt")
-    if precision == "f16x1" and (L * nsamp) % 16 != 0:
-        raise ValueError(f"the f16 throughput kernel (ROBIR_PRECISION=f16) exists in the tile-list form only: L*nsamp = {L}*{nsamp} must be a "
-                         "multiple of 16 -- use ROBIR_PRECISION=exact for this light")
-    # "f16x3-v2" = second-generation split-precision kernel: two tiles per wave, one workgroup per CU, head on the matrix
-    # pipe (csrc/vis_diffuse_v2.hip); "f16x3" = first generation: one 16-sample tile per wave, two workgroups per CU,
-    # weights staged by LDS-DMA; "f16x6*" = exact three-piece operands: "-1t" round 3's one tile per wave, one workgroup per point
-    # (csrc/vis_diffuse_x6.hip); "-pt" two tiles per wave, one workgroup per point; "-stream" two tiles per wave, persistent grid
-    # over the global tile list (both csrc/vis_diffuse_x6t.hip, bit-identical to each other)
-    n = normals.shape[0]
-    out = torch.empty(n, L, dtype=torch.float32, device=normals.device)
+    n, dev = normals.shape[0], normals.device
+    r = dispatch.dvis(precision, n, L, nsamp, DVIS_X6_FORM, DVIS_X6_FP8, DVIS_F16_GEN, lambda: chunk_ids_ascending(chunk_id),
+                      DVIS_STREAM_MAX_POINTS, DVIS_STREAM_SHORT_LIST)
+    out = torch.empty(n, L, dtype=torch.float32, device=dev)
     if chunk_id is not None:
         assert chunk_id.dtype == torch.int32
-    if precision in ("f16x3-v3", "f16x6-stream", "f16x1"):
-        # streaming form: global tile list + persistent grid (csrc/vis_diffuse_v3.hip, vis_diffuse_x6t.hip); scratch sized for the
-        # worst case (every direction front-facing) so that nothing has to be read back to the host
-        LS = L * nsamp
-        dev = normals.device
-        if precision == "f16x1" and DVIS_F16_GEN == 3 and chunk_ids_ascending(chunk_id):
-            # point-block form: scratch by items (a block of 16 points, two items where a block spans a chunk boundary)
-            n_chunks = max(1, dirs.shape[0] // LS)
-            items_max = (n + 15) // 16 + n_chunks - 1
-            entries = torch.empty(items_max * LS, dtype=torch.int32, device=dev)
-            pair_vis = torch.empty(items_max * LS * 16, dtype=torch.float32, device=dev)
-            round_info = torch.empty(items_max * LS // 16, 4, dtype=torch.int32, device=dev)
-            item_info = torch.empty(items_max, 4, dtype=torch.int32, device=dev)
-            counters = torch.empty(4, dtype=torch.int64, device=dev)
-            call("rb_dvis_pblock_f16", ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
-                 ptr(split["hidden_f16_head"]), c_int(L), c_int(nsamp), c_int(1 if argmax_vis else 0), c_int(items_max), ptr(entries),
-                 ptr(pair_vis), ptr(round_info), ptr(item_info), ptr(counters), c_int(DVIS_STREAM_WORKGROUPS), ptr(out), ptr(eval_count),
-                 stream_ptr())
-            if os.environ.get("ROBIR_RANGE_CHECK", "") == "sync" and int(counters[3].item()) != 0:
-                # counters[3]: chunk ids not ascending (a list whose order was only ASSERTED through the `_robir_ascending` attribute) or more
-                # items than the scratch holds -- the kernel then leaves its NaN fill in `out`.  Read in the debug mode only: a host sync.
-                raise _lib.RobirHipError("rb_dvis_pblock_f16: chunk ids are not ascending or the item scratch overflowed -- the outputs "
-                                         "of this call are NaN (ADVICE r5; run without the `_robir_ascending` tag to let ops check the order)")
-            return out
+    args = [ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum), ptr(split[r.blob])]
+    if r.layout == "gen1":      # rb_dvis_fused: the output layer in row-major form, precision code 5 = the split-precision kernel
+        args += [ptr(split["w_last"]), ptr(split["b_last"])]
+    args += [c_int(L), c_int(nsamp), c_int(1 if argmax_vis else 0)]
+    if r.layout == "gen1":
+        args.append(c_int(5 if r.legacy else 0))
+    if r.fmt is not None:
+        args.append(c_int(split[r.fmt] if isinstance(r.fmt, str) else r.fmt))
+    LS = L * nsamp
+    # the tile-list forms: scratch sized for the worst case (every direction front-facing) so that nothing has to be read back to the host
+    if r.layout == "pblock":      # by items: a block of 16 points, two items where a block spans a chunk boundary
+        items_max = (n + 15) // 16 + max(1, dirs.shape[0] // LS) - 1
+        entries = torch.empty(items_max * LS, dtype=torch.int32, device=dev)
+        pair_vis = torch.empty(items_max * LS * 16, dtype=torch.float32, device=dev)
+        round_info = torch.empty(items_max * LS // 16, 4, dtype=torch.int32, device=dev)
+        item_info = torch.empty(items_max, 4, dtype=torch.int32, device=dev)
+        counters = torch.empty(4, dtype=torch.int64, device=dev)
+        args += [c_int(items_max), ptr(entries), ptr(pair_vis), ptr(round_info), ptr(item_info), ptr(counters), c_int(DVIS_STREAM_WORKGROUPS)]
+    elif r.layout == "stream":      # global tile list + persistent grid (csrc/vis_diffuse_v3.hip, vis_diffuse_x6t.hip, vis_diffuse_f16t.hip)
         pair_j = torch.empty(n * LS, dtype=torch.int16, device=dev)
         pair_vis = torch.empty(n * LS, dtype=torch.float32, device=dev)
         tile_info = torch.empty(n * LS // 16, 2, dtype=torch.int32, device=dev)
         point_info = torch.empty(n, 2, dtype=torch.int32, device=dev)
         counters = torch.empty(2, dtype=torch.int64, device=dev)
-        x6 = precision in ("f16x6-stream", "f16x1")      # "f16x1": plain f16, one product (csrc/vis_diffuse_f16t.hip): NARROWER than fp32
-        blob, fmt = split["hidden_x6_head" if x6 else "hidden_h3_head"], split["x6_head_scale_log2" if x6 else "h3_head_scale_log2"]
-        if precision == "f16x6-stream" and DVIS_X6_FP8:
-            blob, fmt = split["hidden_x6_head_fp8"], 8
-        if precision == "f16x1" and DVIS_F16_GEN >= 2:
-            blob, fmt = split["hidden_f16_head"], 1       # rb_dvis_stream_f16: format 1 = the h-only blob -> second-generation kernel
-        call("rb_dvis_stream_f16" if precision == "f16x1" else ("rb_dvis_stream_x6" if x6 else "rb_dvis_stream"), ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
-             ptr(blob), c_int(L), c_int(nsamp), c_int(1 if argmax_vis else 0),
-             c_int(fmt), ptr(pair_j), ptr(pair_vis), ptr(tile_info), ptr(point_info), ptr(counters),
-             c_int(DVIS_STREAM_WORKGROUPS), ptr(out), ptr(eval_count), stream_ptr())
-        return out
-    if precision in X6:
-        fp8 = DVIS_X6_FP8 and precision != "f16x6-1t"
-        call("rb_dvis_fused_x6" if precision == "f16x6-1t" else "rb_dvis_fused_x6t", ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
-             ptr(split["hidden_x6_head_fp8" if fp8 else "hidden_x6_head"]), c_int(L), c_int(nsamp), c_int(1 if argmax_vis else 0),
-             c_int(8 if fp8 else split["x6_head_scale_log2"]), ptr(out), ptr(eval_count), stream_ptr())
-        return out
-    if precision == "f16x3-v2":
-        call("rb_dvis_fused_v2", ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
-             ptr(split["hidden_h3_head"]), c_int(L), c_int(nsamp), c_int(1 if argmax_vis else 0),
-             c_int(split["h3_head_scale_log2"]), ptr(out), ptr(eval_count), stream_ptr())
-        return out
-    # precision 5 = the first-generation split-precision kernel: compiled into the legacy library only
-    (_lib.call_legacy if h3 else call)("rb_dvis_fused", ptr(normals), ptr(chunk_id), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
-         ptr(split["hidden_h3"] if h3 else split["hidden"]), ptr(split["w_last"]), ptr(split["b_last"]), c_int(L),
-         c_int(nsamp), c_int(1 if argmax_vis else 0), c_int(5 if h3 else 0), c_int(split["h3_scale_log2"] if h3 else 0),
-         ptr(out), ptr(eval_count), stream_ptr())
+        args += [ptr(pair_j), ptr(pair_vis), ptr(tile_info), ptr(point_info), ptr(counters), c_int(DVIS_STREAM_WORKGROUPS)]
+    (_lib.call_legacy if r.legacy else call)(r.entry, *args, ptr(out), ptr(eval_count), stream_ptr())
+    if r.layout == "pblock" and os.environ.get("ROBIR_RANGE_CHECK", "") == "sync" and int(counters[3].item()) != 0:
+        # counters[3]: chunk ids not ascending (a list whose order was only ASSERTED through the `_robir_ascending` attribute) or more
+        # items than the scratch holds -- the kernel then leaves its NaN fill in `out`.  Read in the debug mode only: a host sync.
+        raise _lib.RobirHipError("rb_dvis_pblock_f16: chunk ids are not ascending or the item scratch overflowed -- the outputs "
+                                 "of this call are NaN (ADVICE r5; run without the `_robir_ascending` tag to let ops check the order)")
     return out
+
+
+def _spec_vis_buffers(n, ns, n_chunks, dev):
+    """Outputs and scratch of the two spec_vis_sample forms: sharpness [n], per-chunk minimum, directions, weights, front-facing flags."""
+    return (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n_chunks, dtype=torch.int32, device=dev),
+            torch.empty(n * ns, 3, dtype=torch.float32, device=dev), torch.empty(n * ns, dtype=torch.float32, device=dev),
+            torch.empty(n * ns, dtype=torch.uint8, device=dev))
 
 
 def spec_vis_sample(normal, view, rough, chunk_id, n_chunks, u_theta, u_phi):
     normal, view, rough = _f32(normal), _f32(view), _f32(rough).reshape(-1)
     u_theta, u_phi = _f32(u_theta), _f32(u_phi)
     n, ns = u_theta.shape
-    dev = normal.device
-    sharp = torch.empty(n, dtype=torch.float32, device=dev)
-    cmin = torch.empty(n_chunks, dtype=torch.int32, device=dev)
-    dirs = torch.empty(n * ns, 3, dtype=torch.float32, device=dev)
-    wts = torch.empty(n * ns, dtype=torch.float32, device=dev)
-    front = torch.empty(n * ns, dtype=torch.uint8, device=dev)
+    sharp, cmin, dirs, wts, front = _spec_vis_buffers(n, ns, n_chunks, normal.device)
     call("rb_spec_vis_sample", ptr(normal), ptr(view), ptr(rough), ptr(chunk_id), c_long(n), c_int(n_chunks), c_int(ns),
          ptr(u_theta), ptr(u_phi), ptr(sharp), ptr(cmin), ptr(dirs), ptr(wts), ptr(front), stream_ptr())
     return dirs, wts, front
@@ -702,12 +621,7 @@ def spec_vis_sample_lobes(normal, view, lobes, lambdas, chunk_id, n_chunks, u_th
     u_theta, u_phi = _f32(u_theta), _f32(u_phi)
     n, ns = u_theta.shape
     assert lobes.shape == (n, 3) and lambdas.shape == (n,), (lobes.shape, lambdas.shape)
-    dev = normal.device
-    sharp = torch.empty(n, dtype=torch.float32, device=dev)
-    cmin = torch.empty(n_chunks, dtype=torch.int32, device=dev)
-    dirs = torch.empty(n * ns, 3, dtype=torch.float32, device=dev)
-    wts = torch.empty(n * ns, dtype=torch.float32, device=dev)
-    front = torch.empty(n * ns, dtype=torch.uint8, device=dev)
+    sharp, cmin, dirs, wts, front = _spec_vis_buffers(n, ns, n_chunks, normal.device)
     call("rb_spec_vis_sample_lobes", ptr(normal), ptr(view), ptr(lobes), ptr(lambdas), ptr(chunk_id), c_long(n), c_int(n_chunks), c_int(ns),
          ptr(u_theta), ptr(u_phi), ptr(sharp), ptr(cmin), ptr(dirs), ptr(wts), ptr(front), stream_ptr())
     return dirs, wts, front
@@ -720,6 +634,13 @@ def spec_vis_reduce(logits, front, wts, n, nsamp, inv, argmax_vis, testing):
     return bvis
 
 
+def _f0_tensor(f0, dev):
+    """f0 as a device tensor holding the scalar |specular_reflectance| (read by the kernel -- no host copy, no cache to go stale)."""
+    if isinstance(f0, torch.Tensor):
+        return f0.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
+    return torch.full((1,), float(f0), device=dev)
+
+
 def sg_shade(normal, view, lgt, f0, rough, albedo, bvis, light_vis=None, metallic=None, indir_integral=None,
              lin_diff=False, want_shadow=False):
     normal, view, lgt, albedo = _f32(normal), _f32(view), _f32(lgt), _f32(albedo)
@@ -730,9 +651,7 @@ def sg_shade(normal, view, lgt, f0, rough, albedo, bvis, light_vis=None, metalli
     dev = normal.device
     rgb, spec, diff = (torch.empty(n, 3, dtype=torch.float32, device=dev) for _ in range(3))
     shadow = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_shadow else None
-    # f0: device tensor holding the scalar |specular_reflectance| (read by the kernel -- no host copy, no cache to go stale)
-    f0 = (f0.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous() if isinstance(f0, torch.Tensor)
-          else torch.full((1,), float(f0), device=dev))
+    f0 = _f0_tensor(f0, dev)
     call("rb_sg_shade", ptr(normal), ptr(view), ptr(lgt), c_int(1 if per_point else 0), c_int(M), ptr(f0), ptr(rough),
          ptr(albedo), ptr(_f32(metallic).reshape(-1) if metallic is not None else None),
          ptr(_f32(light_vis) if light_vis is not None else None), ptr(bvis),
@@ -754,8 +673,7 @@ def sg_shade_backward(normal, view, lgt, f0, rough, albedo, bvis, spec, diff, g_
     per_point = lgt.dim() == 3
     M = lgt.shape[-2]
     dev = normal.device
-    f0 = (f0.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous() if isinstance(f0, torch.Tensor)
-          else torch.full((1,), float(f0), device=dev))
+    f0 = _f0_tensor(f0, dev)
     metallic = _f32(metallic).reshape(-1) if metallic is not None else None
     light_vis = _f32(light_vis) if light_vis is not None else None
     indir_integral = _f32(indir_integral) if indir_integral is not None else None
@@ -825,7 +743,7 @@ def octree_cast_batched(T, origins, per_ray_origin, dirs, batch, max_iter, step,
     return x, hit.bool(), t, sched
 
 
-CAST_ONE_LAUNCH = _os.environ.get("ROBIR_CAST_ONE_LAUNCH", "1") == "1"    # the persistent-grid form of the general lock-step cast
+CAST_ONE_LAUNCH = os.environ.get("ROBIR_CAST_ONE_LAUNCH", "1") == "1"    # the persistent-grid form of the general lock-step cast
 CAST_COOP_REFUSED = 0              # how often the cooperative launch was refused and the per-iteration launches took over
 CAST_ONE_LAUNCH_MAX_RAYS = 16384   # above this the per-iteration launches fill the chip and win (tools/ab_cast.py: 60 k rays 1.3 vs 2.1 ms)
 
@@ -884,7 +802,7 @@ def octree_cast_general(T, origins, dirs, max_iter, step, check_every=16, max_to
 
 
 LAST_OCTREE_VIS_LAYOUT = None
-OVIS_COMPACT = _os.environ.get("ROBIR_OVIS_COMPACT", "1") == "1"   # stable compaction of the active rays between iterations
+OVIS_COMPACT = os.environ.get("ROBIR_OVIS_COMPACT", "1") == "1"   # stable compaction of the active rays between iterations
 OVIS_CHUNKS_PER_CALL = 48       # chunks per traced-visibility launch group: bounds the scratch (28 B per pair slot) to ~5.6 GB
 
 
@@ -1121,14 +1039,12 @@ def cesr_net_h3(X, M, kind, blob, scale_log2, n_label=1):
 
 def cesr_net_points(x, M, kind, blob, n_label=1, scale_log2=None, ring=None):
     """cesr_net / cesr_net_h3 on PE10(x) with the encoding fused (kind 0: M = points; kind 2: M = points * n_label rows).
-    ring (split precision; default: by batch size): the chunk-stream kernel (csrc/wide_ring.h) -- bit-identical outputs."""
+    ring (split precision; the default): the chunk-stream kernel (csrc/wide_ring.h) -- bit-identical outputs."""
     x = _f32(x)
     Y = torch.empty(M, 3 if kind == 0 else 2, dtype=torch.float32, device=x.device)
-    if ring is None:
-        ring = M >= WIDE_RING_MIN_ROWS
     if scale_log2 is None:
         call("rb_cesr_net_points", ptr(x), c_long(M), c_int(kind), c_int(n_label), ptr(blob), ptr(Y), stream_ptr())
-    elif ring:
+    elif ring is None or ring:
         call("rb_cesr_net_ring_points", ptr(x), c_long(M), c_int(kind), c_int(n_label), ptr(blob), c_int(scale_log2), ptr(Y), c_int(0),
              stream_ptr())
     else:

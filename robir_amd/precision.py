@@ -30,6 +30,18 @@ POLICIES = {"exact": ("f16x6", "f16x6"), "split": ("f16x3-auto", "f16x3"), "f16"
 VIS_MODES = ("fp32", "f16x6", "f16x3-auto", "f16x3-v3", "f16x3-v2", "f16x3", "f16x1", "f16x6-1t", "f16x6-pt", "f16x6-stream")
 
 
+VALID = {"ROBIR_MLP_PRECISION": (("f16x3", "fp32", "f16x6"), "f16x6, fp32 or f16x3"),
+         "ROBIR_CESR_PRECISION": (("f16x1", "f16x3", "fp32", "f16x6"), "f16x1, f16x6, fp32 or f16x3"),
+         "ROBIR_VIS_PRECISION": (VIS_MODES, "one of " + ", ".join(VIS_MODES))}
+
+
+def check(variable, p):
+    """p if it is a value of `variable`, else the ValueError (robir_amd.dispatch raises the same for a string handed to it directly)."""
+    if p not in VALID[variable][0]:
+        raise ValueError(f"{variable} must be {VALID[variable][1]}")
+    return p
+
+
 def policy():
     p = os.environ.get("ROBIR_PRECISION", "exact")
     if p not in POLICIES:
@@ -41,10 +53,7 @@ def mlp_precision():
     """Arithmetic of the stand-alone MLP kernels (SDF, colour, visibility, 512-wide nets): 'f16x6' (exact three-piece operands where
     such a kernel exists -- SDF, colour, visibility MLP -- and the f32-input MFMA elsewhere), 'fp32' (f32-input MFMA everywhere) or
     'f16x3' (split precision)."""
-    p = os.environ.get("ROBIR_MLP_PRECISION") or POLICIES[policy()][1]
-    if p not in ("f16x3", "fp32", "f16x6"):
-        raise ValueError("ROBIR_MLP_PRECISION must be f16x6, fp32 or f16x3")
-    return p
+    return check("ROBIR_MLP_PRECISION", os.environ.get("ROBIR_MLP_PRECISION") or POLICIES[policy()][1])
 
 
 def cesr_precision():
@@ -54,15 +63,10 @@ def cesr_precision():
     p = os.environ.get("ROBIR_CESR_PRECISION")
     if p is None:
         p = "f16x1" if (policy() == "f16" and not os.environ.get("ROBIR_MLP_PRECISION")) else mlp_precision()
-    if p not in ("f16x1", "f16x3", "fp32", "f16x6"):
-        raise ValueError("ROBIR_CESR_PRECISION must be f16x1, f16x6, fp32 or f16x3")
-    return p
+    return check("ROBIR_CESR_PRECISION", p)
 
 
 def vis_precision():
     """Arithmetic of the fused light-visibility kernel at import time of robir_amd.sg_render (its VIS_PRECISION attribute is
     what is read per call)."""
-    p = os.environ.get("ROBIR_VIS_PRECISION") or POLICIES[policy()][0]
-    if p not in VIS_MODES:
-        raise ValueError("ROBIR_VIS_PRECISION must be one of " + ", ".join(VIS_MODES))
-    return p
+    return check("ROBIR_VIS_PRECISION", os.environ.get("ROBIR_VIS_PRECISION") or POLICIES[policy()][0])

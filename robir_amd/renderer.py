@@ -21,7 +21,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import deferred, ops, sg_render
+from . import deferred, dispatch, ops, sg_render
+from .precision import cesr_precision, mlp_precision
 from .nets import (ImplicitNetworkMy, IndirctIllumNetwork, VisNetwork, EnvmapMaterialNetwork, GammaCorrect,
                    forward_only_guard)
 from .octree_tracing import OctreeTracing
@@ -518,14 +519,12 @@ class CESRHook:
         normals = ops.normalize3(m.get_idr_render(points, normal_only=True).contiguous(), 1e-4, 1)
         mat = m.envmap_material_network(points, train_spec=True,
                                         noise={"spec": draws.get("spec_randn"), "normal": draws.get("normal_randn")})
-        if ops.SDF_FUSED_PE:        # shadow_net / normal_net straight from the points (encoding inside the kernels)
-            pts = points.float().contiguous()
-            logits = self.shadow_net.eval_point_labels(pts, 128)
-            normal_new = ops.normalize3(self.normal_net._cesr_points(pts, pts.shape[0], 0), 1e-4, 1)
-        else:
-            Xp = ops.feat_pe10(points.float().contiguous())
-            logits = self.shadow_net.eval_point_labels(Xp, 128)
-            normal_new = ops.normalize3(self.normal_net._cesr(Xp, Xp.shape[0], 0), 1e-4, 1)
+        x = points.float().contiguous()
+        rows = dispatch.cesr(mlp_precision(), cesr_precision(), ops.SDF_FUSED_PE, points=True).encode
+        if rows:        # else shadow_net / normal_net straight from the points (encoding inside the kernels)
+            x = ops.feat_pe10(x)
+        logits = self.shadow_net.eval_point_labels(x, 128)
+        normal_new = ops.normalize3((self.normal_net._cesr if rows else self.normal_net._cesr_points)(x, x.shape[0], 0), 1e-4, 1)
         diffuse_vis = ops.softmax2(logits, 1)
         albedo = mat["sg_diffuse_albedo"]
         ret = sg_render.render_with_all_sg(points=points, normal=normal_new if self.cur_iter > 1000 else mat["sg_normal_map"],

@@ -25,7 +25,7 @@ import math
 import numpy as np
 import torch
 
-from . import ops, sg_autograd
+from . import dispatch, ops, sg_autograd
 from .nets import VisNetwork
 from .octree_tracing import OctreeVisModel
 
@@ -39,7 +39,6 @@ OCTREE_VIS_BATCH = 2000000      # pairs per VisModel call of the reference (sg_r
 #                throughput mode, tests/test_precision_gpu.py anchors it on float64) with the kernel generation picked by
 #                launch size: "f16x3-v3" (global tile list + persistent grid) for small launches, "f16x3-v2" (one point per
 #                workgroup) for whole views -- bit-identical to each other; "f16x3" = first generation.
-import os as _os
 from .precision import vis_precision as _vis_precision
 VIS_PRECISION = _vis_precision()
 
@@ -149,12 +148,10 @@ def _diffuse_vis_core(points, normals, VisModel, lgt, u_t, u_p, thr, argmax_vis,
     dirs, wdir, wsum = ops.dvis_dirs(lgt, u_t.to(dev), u_p.to(dev), thr, direct=direct)
     if isinstance(VisModel, VisNetwork):
         sp = VisModel.packed_split()
-        if ops.SDF_FUSED_PE:       # first-layer halves straight from the points / directions (encoding fused)
-            A = ops.linear_pe10_256(points.float().contiguous(), sp["point"])
-            Bd = ops.linear_pe10_256(dirs, sp["dir"])
-        else:
-            A = ops.linear_64_256(ops.feat_pe10(points.float().contiguous()), sp["point"])
-            Bd = ops.linear_64_256(ops.feat_pe10(dirs), sp["dir"])
+        r = dispatch.vis_halves(ops.SDF_FUSED_PE)       # first-layer halves straight from the points / directions, or from PE rows
+        half, rows = getattr(ops, r.fn), (ops.feat_pe10 if r.encode else (lambda t: t))
+        A = half(rows(points.float().contiguous()), sp["point"])
+        Bd = half(rows(dirs), sp["dir"])
         cnt = None
         if stats is not None:
             cnt = stats.setdefault("diffuse_vis_evals", torch.zeros(1, dtype=torch.int64, device=dev))
