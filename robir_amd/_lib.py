@@ -30,12 +30,15 @@ ABI_VERSION = 8
 TRAIN_PATH = os.path.join(_HERE, "librobir_hip_train.so")
 _train = None
 TRAIN_ABI_VERSION = 1
+VISTRAIN_PATH = os.path.join(_HERE, "librobir_hip_vistrain.so")
+_vistrain = None
+VISTRAIN_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
     """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library), librobir_hip_train.so (the
-    training-side kernels, csrc/train/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel generations,
-    csrc/Makefile)."""
+    training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/) and -- legacy=True --
+    librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j", jobs, "all" if legacy else "default"],
@@ -109,6 +112,35 @@ def call_train(name, *args):
     rc = fn(*args)
     if rc != 0:
         raise RobirHipError(f"{name} failed ({rc}): {L.rb_train_last_error().decode()}")
+
+
+def vistrain():
+    """The visibility-training library (include/robir_hip_vistrain.h; `make -C robir_amd/csrc vistrain`): the reverse mode of VisNetwork.
+    Its own loader and its own error text, like train()."""
+    global _vistrain
+    if _vistrain is None:
+        if not os.path.exists(VISTRAIN_PATH):
+            raise RobirHipError(f"{VISTRAIN_PATH} not found: the VISIBILITY-TRAINING library librobir_hip_vistrain.so (visibility-network "
+                                "gradients, robir_amd/vis_autograd.py) is built by `python -c 'import __graft_entry__ as g; g.build()'` or "
+                                "`make -C robir_amd/csrc vistrain` -- there is no PyTorch fallback for its kernels")
+        L = ctypes.CDLL(VISTRAIN_PATH)
+        L.rb_vt_last_error.restype = ctypes.c_char_p
+        L.rb_vt_vis_bwd_scratch_bytes.restype = ctypes.c_long
+        if L.rb_vt_abi_version() != VISTRAIN_ABI_VERSION:
+            raise RobirHipError("librobir_hip_vistrain.so ABI version mismatch")
+        _vistrain = L
+    return _vistrain
+
+
+def call_vistrain(name, *args):
+    """An entry point of the visibility-training library (never resolved against the other three)."""
+    L = vistrain()
+    fn = getattr(L, name, None)
+    if fn is None:
+        raise RobirHipError(f"{name} is not exported by librobir_hip_vistrain.so")
+    rc = fn(*args)
+    if rc != 0:
+        raise RobirHipError(f"{name} failed ({rc}): {L.rb_vt_last_error().decode()}")
 
 
 def legacy_loaded():

@@ -11,7 +11,8 @@ a parameter that requires grad, raises ForwardOnlyError (`forward_only_guard`; t
 --plot_only rendering) instead of handing detached outputs to a loss.  Material NETWORKS therefore still train on
 the reference's modules; what IS differentiable on the HIP path is the SG shading of their outputs (robir_amd/sg_autograd.py,
 sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis) and -- after the explicit
-opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py).
+opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py), and -- after
+robir_amd.training.enable_visibility_training -- the visibility network (robir_amd/vis_autograd.py).
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """
@@ -70,8 +71,9 @@ PRECISE_GRAD_SPLIT = os.environ.get("ROBIR_PRECISE_GRAD", "split") == "split"   
 def forward_only_guard(module):
     """The HIP kernels have no backward: a training-mode call that autograd would have to differentiate must not silently
     return detached tensors (loss.backward() would then train only whatever still carries a graph).  A module marked by
-    robir_amd.training.enable_material_training has a backward and passes; its unmarked sub-networks still raise."""
-    if getattr(module, "_material_training", False):
+    robir_amd.training.enable_material_training (or, a VisNetwork, by enable_visibility_training) has a backward and passes; its unmarked
+    sub-networks still raise."""
+    if getattr(module, "_material_training", False) or getattr(module, "_visibility_training", False):
         return
     if module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise ForwardOnlyError(f"{type(module).__name__}: robir_amd kernels are forward-only -- call .eval(), wrap the call in "
@@ -149,9 +151,18 @@ class VisNetwork(nn.Module):
 
     packed_full, packed_full_h3, packed_full_x6, packed_split = (_blob_alias(k) for k in ("full", "full_h3", "full_x6", "split"))
 
+    def _trainable(self):
+        """Marked by robir_amd.training.enable_visibility_training, grad mode on, a parameter that requires grad: calls build a graph."""
+        return (getattr(self, "_visibility_training", False) and torch.is_grad_enabled()
+                and any(p.requires_grad for p in self.parameters()))
+
     def logits_from_features(self, X):
         """X [M,128] = [PE10(p) | PE10(d)] (ops.feat_vis) -> logits [M,2]; arithmetic per robir_amd.MLP_PRECISION."""
         forward_only_guard(self)
+        if self._trainable():
+            raise NotImplementedError("VisNetwork.logits_from_features: the HIP backward of the visibility network encodes the points and the "
+                                      "directions itself (fp64 from the fp32 coordinates) -- call logits_from_points / forward while the network "
+                                      "is marked by enable_visibility_training, or wrap the feature-row call in torch.no_grad()")
         r = dispatch.vis_mlp(mlp_precision(), ops.SDF_FUSED_PE, points=False)
         return getattr(ops, r.fn)(X, self._blob(r.blob), **_h3(r))
 
@@ -159,6 +170,9 @@ class VisNetwork(nn.Module):
         """points [M/rep,3], dirs [M,3] (rep consecutive directions per point) -> logits [M,2]: [PE10(p) | PE10(d)] is encoded
         inside the MLP kernel (no feature rows) unless ROBIR_SDF_FUSED_PE=0."""
         forward_only_guard(self)
+        if self._trainable():
+            from . import vis_autograd
+            return vis_autograd.logits(self, points, dirs, rep)
         r = dispatch.vis_mlp(mlp_precision(), ops.SDF_FUSED_PE, points=True)
         if r.encode:
             return self.logits_from_features(ops.feat_vis(points.float().contiguous(), dirs.float().contiguous(), rep=rep))

@@ -496,6 +496,46 @@ def ae_backward(X, params, g_out=None, g_out_xi=None, g_raw=None, noise=None, va
     return out, {"launches": int(stats[0]), "encoder_pass": bool(stats[1]), "scratch_bytes": nbytes}
 
 
+VIS_PARAM_NAMES = tuple(f"vis_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias"))
+# A full slab's widest weight gradient (256 x 257: 20 output tiles) is 20 * 16384 / 1024 = 320 workgroups on 256 compute units, and the
+# scratch is 227 MB whatever the batch (profiles/vis_backward_times.md)
+VIS_SLAB_ROWS = 16384
+VIS_PART_ROWS = 1024
+
+
+def vis_backward(points, dirs, rep, params, g_logits, want=VIS_PARAM_NAMES, slab_rows=None, part_rows=None):
+    """Reverse mode of VisNetwork (rb_vt_vis_bwd, include/robir_hip_vistrain.h): points [M/rep,3], dirs [M,3] (rep consecutive directions per
+    point), params = the ten nn.Linear tensors in VIS_PARAM_NAMES order, g_logits [M,2] the upstream gradient on the logits.  -> (dict name ->
+    gradient in the parameter's own shape for the names in `want`, stats dict: kernels enqueued, lowest layer differentiated, partitions per
+    full slab, scratch bytes).  Allocates the wanted gradients and the scratch, nothing else."""
+    points, dirs = _f32(points.detach()), _f32(dirs.detach())
+    M, dev = dirs.shape[0], dirs.device
+    rep = int(rep)
+    assert dirs.dim() == 2 and dirs.shape[1] == 3 and rep >= 1 and points.shape[0] * rep == M and len(params) == 10
+    params = [_f32(p.detach()) for p in params]
+    g_logits = _f32(g_logits.detach()).reshape(M, 2)
+    unknown = set(want) - set(VIS_PARAM_NAMES)
+    if unknown:
+        raise KeyError(f"vis_backward: no such parameter: {sorted(unknown)}")
+    alloc = torch.zeros if M == 0 else torch.empty           # M > 0: k_finish stores every element of every wanted gradient
+    out = {k: alloc(p.shape, dtype=torch.float32, device=dev) for k, p in zip(VIS_PARAM_NAMES, params) if k in want}
+    slab = int(slab_rows or VIS_SLAB_ROWS)
+    part = int(part_rows or min(slab, VIS_PART_ROWS))
+    stats = (c_int * 3)(0, 5, 0)
+    nbytes = 0
+    if M > 0 and out:
+        L = _lib.vistrain()
+        nbytes = int(L.rb_vt_vis_bwd_scratch_bytes(c_long(M), c_long(slab), c_long(part)))
+        if nbytes < 0:
+            raise _lib.RobirHipError("rb_vt_vis_bwd_scratch_bytes: " + L.rb_vt_last_error().decode())
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        P = (ctypes.c_void_p * 10)(*[p.data_ptr() for p in params])
+        G = (ctypes.c_void_p * 10)(*[out[k].data_ptr() if k in out else None for k in VIS_PARAM_NAMES])
+        _lib.call_vistrain("rb_vt_vis_bwd", ptr(points), ptr(dirs), c_long(M), c_int(rep), P, ptr(g_logits), G, c_long(slab), c_long(part),
+                           ptr(scratch), c_long(nbytes), stats, stream_ptr())
+    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+
+
 def axpy(a, b, s):
     a, b = _f32(a), _f32(b)
     y = torch.empty_like(a)

@@ -430,7 +430,13 @@ class IDRNetwork(nn.Module):
         calling trace_radiance once per 1024-pixel chunk (training/train_visibility.py); without it the call is ONE batch, like
         one reference call."""
         forward_only_guard(self)
-        if (isinstance(input, deferred.ChunkOutputs) and not input._dirty and test_dir is None and draws is None and chunk is None):
+        # a visibility network marked by training.enable_visibility_training, in grad mode: pred_vis carries a graph to its parameters
+        # (the scatter below is ordinary torch), so the call runs at once -- a recorded pass runs under no_grad and would drop the graph
+        vis_graph = self.visibility_network._trainable()
+        if vis_graph:
+            self.flush()
+        if (not vis_graph and isinstance(input, deferred.ChunkOutputs) and not input._dirty and test_dir is None and draws is None
+                and chunk is None):
             # the outputs of a RECORDED chunk forward, default arguments (the runners' per-chunk `trace_radiance(out, nsamp=8)`,
             # training/train_cesr.py:321-326, train_visibility.py): recorded as well -- it runs behind the pass as one grouped call, every
             # chunk its own lock-step batch, with the draws the per-chunk calls would take (robir_amd/deferred.py)

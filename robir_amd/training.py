@@ -10,7 +10,12 @@ EnvmapMaterialNetwork.  With the mark, grad mode on and a parameter that require
   * SparseAE.encode of the marked auto-encoder is differentiable (the KL term's input);
   * train_spec=False detaches the material outputs like the reference does.
 
-kl_sparsity / latent_smooth restate the two stage-3 regularisers of model/loss.py:61-95 on tensors (a few reductions: plumbing)."""
+kl_sparsity / latent_smooth restate the two stage-3 regularisers of model/loss.py:61-95 on tensors (a few reductions: plumbing).
+
+The same opt-in exists for the "Vis" stage (training/train_visibility.py:297-308: the optimiser holds visibility_network):
+enable_visibility_training marks a VisNetwork.  With the mark, grad mode on and a parameter that requires grad, VisNetwork.forward /
+logits_from_points return logits with a graph to the ten nn.Linear tensors (robir_amd/vis_autograd.py -> librobir_hip_vistrain.so), and
+IDRNetwork.trace_radiance's pred_vis carries that graph; visibility_loss restates the stage's cross-entropy (model/loss.py:173-177)."""
 import torch
 
 from . import nets
@@ -66,3 +71,37 @@ def latent_smooth(out):
     d_diff, d_rough = pick("diffuse_albedo"), pick("roughness")[..., 0]
     d_xi_diff, d_xi_rough = out["random_xi_diffuse_albedo"], out["random_xi_roughness"][..., 0]
     return torch.mean(torch.abs(d_diff - d_xi_diff)) + torch.mean(torch.abs(d_rough - d_xi_rough)) * 0.2
+
+
+def _visibility_network(obj):
+    if isinstance(obj, nets.VisNetwork):
+        return obj
+    net = getattr(obj, "visibility_network", None)
+    if isinstance(net, nets.VisNetwork):
+        return net
+    return None
+
+
+def enable_visibility_training(net, on=True):
+    """Mark (on=False: unmark) a VisNetwork -- or the one a model holds as .visibility_network -- as trainable on the HIP path.  Returns the
+    visibility network.  The fused consumers of its weights (the light-visibility kernel, the BRDF-lobe visibilities, the CESR hook) stay
+    non-differentiable; they read parameter-version-keyed blobs and see an optimiser step on their next call."""
+    vis = _visibility_network(net)
+    if vis is None:
+        raise TypeError(f"enable_visibility_training: {type(net).__name__} is neither a VisNetwork nor a model that has one")
+    vis._visibility_training = bool(on)
+    return vis
+
+
+def visibility_training_enabled(net):
+    return bool(getattr(_visibility_network(net), "_visibility_training", False))
+
+
+def visibility_loss(pred_vis, gt_vis, points_mask):
+    """The visibility term of IllumLoss.forward (model/loss.py:173-177): nn.CrossEntropyLoss() (mean over the rows) of the logits
+    pred_vis [N,S,2] at the surface points points_mask [N]; the class index is the NEGATED traced label gt_vis [N,S,1] (bool: the secondary
+    ray hit the surface), so class 1 = visible."""
+    mask = points_mask.reshape(-1).bool()
+    pred = pred_vis[mask].reshape(-1, 2)
+    gt = (~gt_vis[mask].bool()).long().reshape(-1)
+    return torch.nn.functional.cross_entropy(pred, gt)
