@@ -85,62 +85,62 @@ def legacy():
     return _legacy
 
 
+def _load_aux(path, abi, prefix, long_queries, target, title, serves):
+    """An auxiliary library: its own file, symbol prefix, ABI version, last-error function, `long`-returning queries and not-found message
+    -- a missing file is reported as such, never as a missing legacy entry point -- and never resolved against another library."""
+    if not os.path.exists(path):
+        raise RobirHipError(f"{path} not found: the {title} ({serves}) is built by `python -c 'import __graft_entry__ as g; g.build()'` "
+                            f"or `make -C robir_amd/csrc {target}` -- there is no PyTorch fallback for its kernels")
+    L = ctypes.CDLL(path)
+    L.prefix = prefix
+    getattr(L, prefix + "last_error").restype = ctypes.c_char_p
+    for name in long_queries:
+        getattr(L, name).restype = ctypes.c_long
+    if getattr(L, prefix + "abi_version")() != abi:
+        raise RobirHipError(f"librobir_hip_{target}.so ABI version mismatch")
+    return L
+
+
+def aux_error(L):
+    """The last-error string of an auxiliary library (every library keeps its own)."""
+    return getattr(L, L.prefix + "last_error")().decode()
+
+
+def _call_aux(L, name, *args):
+    fn = getattr(L, name, None)
+    if fn is None:
+        raise RobirHipError(f"{name} is not exported by {os.path.basename(L._name)}")
+    rc = fn(*args)
+    if rc != 0:
+        raise RobirHipError(f"{name} failed ({rc}): {aux_error(L)}")
+
+
 def train():
-    """The training library (include/robir_hip_train.h; `make -C robir_amd/csrc train`): the reverse mode of the spec auto-encoder.  Its own
-    loader and its own error text -- a missing file is reported as such, never as a missing legacy entry point."""
+    """The training library (include/robir_hip_train.h; `make -C robir_amd/csrc train`): the reverse mode of the spec auto-encoder."""
     global _train
     if _train is None:
-        if not os.path.exists(TRAIN_PATH):
-            raise RobirHipError(f"{TRAIN_PATH} not found: the TRAINING library (material-network gradients, robir_amd/ae_autograd.py) is built "
-                                "by `python -c 'import __graft_entry__ as g; g.build()'` or `make -C robir_amd/csrc train` -- there is no "
-                                "PyTorch fallback for its kernels")
-        L = ctypes.CDLL(TRAIN_PATH)
-        L.rb_train_last_error.restype = ctypes.c_char_p
-        L.rb_train_ae_bwd_scratch_bytes.restype = ctypes.c_long
-        if L.rb_train_abi_version() != TRAIN_ABI_VERSION:
-            raise RobirHipError("librobir_hip_train.so ABI version mismatch")
-        _train = L
+        _train = _load_aux(TRAIN_PATH, TRAIN_ABI_VERSION, "rb_train_", ("rb_train_ae_bwd_scratch_bytes",), "train", "TRAINING library",
+                           "material-network gradients, robir_amd/ae_autograd.py")
     return _train
 
 
 def call_train(name, *args):
-    """An entry point of the training library (never resolved against the other two)."""
-    L = train()
-    fn = getattr(L, name, None)
-    if fn is None:
-        raise RobirHipError(f"{name} is not exported by librobir_hip_train.so")
-    rc = fn(*args)
-    if rc != 0:
-        raise RobirHipError(f"{name} failed ({rc}): {L.rb_train_last_error().decode()}")
+    """An entry point of the training library."""
+    _call_aux(train(), name, *args)
 
 
 def vistrain():
-    """The visibility-training library (include/robir_hip_vistrain.h; `make -C robir_amd/csrc vistrain`): the reverse mode of VisNetwork.
-    Its own loader and its own error text, like train()."""
+    """The visibility-training library (include/robir_hip_vistrain.h; `make -C robir_amd/csrc vistrain`): the reverse mode of VisNetwork."""
     global _vistrain
     if _vistrain is None:
-        if not os.path.exists(VISTRAIN_PATH):
-            raise RobirHipError(f"{VISTRAIN_PATH} not found: the VISIBILITY-TRAINING library librobir_hip_vistrain.so (visibility-network "
-                                "gradients, robir_amd/vis_autograd.py) is built by `python -c 'import __graft_entry__ as g; g.build()'` or "
-                                "`make -C robir_amd/csrc vistrain` -- there is no PyTorch fallback for its kernels")
-        L = ctypes.CDLL(VISTRAIN_PATH)
-        L.rb_vt_last_error.restype = ctypes.c_char_p
-        L.rb_vt_vis_bwd_scratch_bytes.restype = ctypes.c_long
-        if L.rb_vt_abi_version() != VISTRAIN_ABI_VERSION:
-            raise RobirHipError("librobir_hip_vistrain.so ABI version mismatch")
-        _vistrain = L
+        _vistrain = _load_aux(VISTRAIN_PATH, VISTRAIN_ABI_VERSION, "rb_vt_", ("rb_vt_vis_bwd_scratch_bytes",), "vistrain",
+                              "VISIBILITY-TRAINING library librobir_hip_vistrain.so", "visibility-network gradients, robir_amd/vis_autograd.py")
     return _vistrain
 
 
 def call_vistrain(name, *args):
-    """An entry point of the visibility-training library (never resolved against the other three)."""
-    L = vistrain()
-    fn = getattr(L, name, None)
-    if fn is None:
-        raise RobirHipError(f"{name} is not exported by librobir_hip_vistrain.so")
-    rc = fn(*args)
-    if rc != 0:
-        raise RobirHipError(f"{name} failed ({rc}): {L.rb_vt_last_error().decode()}")
+    """An entry point of the visibility-training library."""
+    _call_aux(vistrain(), name, *args)
 
 
 def legacy_loaded():

@@ -8,19 +8,14 @@ the KL term reads).  The backward is ONE call into the training library, which r
 and parameters; ctx.needs_input_grad turns into NULL pointers, an output nobody differentiated into a NULL upstream gradient."""
 import torch
 
-from . import ops
+from . import ops, param_autograd
 
 SLAB_ROWS = ops.AE_SLAB_ROWS      # rows per slab of the backward (bounds its scratch independently of n); tests use small values
 
 
 def refuse_input_grad(**tensors):
-    """points / feature rows / noise are not differentiable on this path: say so instead of returning a zero gradient."""
-    if not torch.is_grad_enabled():
-        return
-    for name, t in tensors.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"robir_amd spec auto-encoder has no gradient with respect to `{name}` (its HIP backward differentiates the "
-                                      f"network parameters only: pass {name}.detach(), or differentiate the input on the reference's modules)")
+    """points / feature rows / noise are not differentiable on this path."""
+    param_autograd.refuse_input_grad("spec auto-encoder", **tensors)
 
 
 def linear_params(ae):
@@ -30,10 +25,7 @@ def linear_params(ae):
 
 
 class SparseAEFn(torch.autograd.Function):
-    """Saved through ctx.save_for_backward, and nothing else: the points (or the feature rows), the noise, `var` and the parameters -- no
-    activation, no output.  Tensors never sit on ctx as plain attributes (output -> grad_fn -> ctx -> output would be a reference cycle that
-    only the cyclic collector frees; autograd checks saved inputs for in-place changes -- an optimiser step between forward and backward is
-    an error, not a silently stale gradient).  ctx keeps the module-independent scalars."""
+    """Saves the points (or the feature rows), the noise, `var` and the parameters (param_autograd: what is saved, and why that way)."""
 
     @staticmethod
     def forward(ctx, ae, x, from_points, noise, *params):
@@ -77,7 +69,7 @@ class SparseAEFn(torch.autograd.Function):
             g_out_xi = None
         grads, _ = ops.ae_backward(X, params, g_out, g_out_xi, g_raw, noise=noise, var=var, latent_act=act, sigmoid_out=sig_out, in_dim=in_dim,
                                    out_dim=out_dim, want=want, slab_rows=slab)
-        return (None, None, None, None, *(grads[k].to(p.dtype) if k in grads else None for k, p in zip(ops.AE_PARAM_NAMES, params)))
+        return param_autograd.backward_result(4, ops.AE_PARAM_NAMES, params, grads)
 
 
 def _apply(ae, x, from_points, noise):

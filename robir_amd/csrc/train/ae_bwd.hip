@@ -1,118 +1,21 @@
 // librobir_hip_train.so: reverse mode of one SparseAE with smooth_on_latent=True (include/robir_hip_train.h).
 //
 // Everything is fp64: the layer activations are recomputed from the fp32 feature rows and the fp32 nn.Linear parameters, the three product
-// families (activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ) run on v_mfma_f64_16x16x4_f64 through ONE tiled kernel (k_gemm64)
-// whose operands are addressed by (row stride, column stride), and each stored gradient is rounded to fp32 once (k_finish).
+// families (activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ) run on v_mfma_f64_16x16x4_f64 through the training libraries' one
+// tiled kernel (k_gemm64 of gemm64.h, instantiated here for LeakyReLU(0.2) and in-place accumulation), and each stored gradient is rounded
+// to fp32 once (k_finish).  This file holds what is particular to the auto-encoder: its element-wise kernels, its plan and its slab loop.
 //
 // Reductions over rows: dW / db of a layer is a GEMM whose REDUCTION dimension is the slab's rows; one thread owns one element of the fp64
 // accumulator (no atomics, no split over rows), slabs are enqueued in order on one stream and add into that element in slab order.  The
 // accumulation order is therefore a function of (n, slab_rows) alone.
 //
 // The decoder's two passes (clean latent | latent + noise * scale) are stacked as 2 S rows of one problem: their weight gradients are one sum.
-#include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 #include "../../../include/robir_hip_train.h"
+#include "gemm64.h"
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 64, BN = 64, BK = 16;      // block tile: four waves, wave w owns rows 16 w .. 16 w + 15 and all 64 columns (4 MFMA tiles)
-constexpr int LDS_LD = 80;                    // doubles per k-row of a tile in LDS: 160 dwords, consecutive k-rows start 32 banks apart
-constexpr double SLOPE = 0.2;                 // nn.LeakyReLU(0.2)
-
-enum { EPI_FWD = 0, EPI_BWD = 1, EPI_ACC = 2 };
-
-struct Gemm {
-    // C[m,n] = sum_k A(m,k) B(k,n);  A(m,k) = A[m sam + k sak], B(k,n) = B[k sbk + n sbn] (fp32 or fp64 elements), zero outside M x K / K x N
-    const void* A; long sam, sak; int a_f32;
-    const void* B; long sbk, sbn; int b_f32;
-    int ones_col;             // >= 0: B(k, ones_col) = 1 for every k < K and no memory is read for that column (db = dZ^T 1 rides along with dW)
-    int M, N, K;
-    int epi;
-    double* C; long ldc;
-    const float* bias;        // EPI_FWD: + bias[n]
-    int lrelu;                // EPI_FWD: LeakyReLU on the result.  EPI_BWD: result *= LeakyReLU'(mask[m,n]), mask = the stored activation
-    const double* mask; long ldm;
-    int first;                // EPI_ACC: 1 = store, 0 = add to what C holds (slab order)
-};
-
-__device__ __forceinline__ double ld_elem(const void* p, long i, int f32) {
-    return f32 ? (double)((const float*)p)[i] : ((const double*)p)[i];
-}
-
-__global__ __launch_bounds__(256) void k_gemm64(Gemm g) {
-    __shared__ double As[BK][LDS_LD];
-    __shared__ double Bs[BK][LDS_LD];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    double4_t acc[4];
-    for (int i = 0; i < 4; ++i) acc[i] = double4_t{0.0, 0.0, 0.0, 0.0};
-    const bool a_kfast = g.sak == 1, b_nfast = g.sbn == 1;
-    for (int k0 = 0; k0 < g.K; k0 += BK) {
-        for (int i = 0; i < 4; ++i) {
-            const int idx = t + 256 * i;
-            int m, k;
-            if (a_kfast) { k = idx & 15; m = idx >> 4; } else { m = idx & 63; k = idx >> 6; }
-            const int gm = m0 + m, gk = k0 + k;
-            As[k][m] = (gm < g.M && gk < g.K) ? ld_elem(g.A, (long)gm * g.sam + (long)gk * g.sak, g.a_f32) : 0.0;
-            int n;
-            if (b_nfast) { n = idx & 63; k = idx >> 6; } else { k = idx & 15; n = idx >> 4; }
-            const int gn = n0 + n;
-            const int gk2 = k0 + k;
-            double v = 0.0;
-            if (gn < g.N && gk2 < g.K) v = gn == g.ones_col ? 1.0 : ld_elem(g.B, (long)gk2 * g.sbk + (long)gn * g.sbn, g.b_f32);
-            Bs[k][n] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 4) {
-            // operand lane map of the 16x16x4 forms: lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]
-            const double a = As[kk + (lane >> 4)][16 * w + (lane & 15)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = Bs[kk + (lane >> 4)][16 * j + (lane & 15)];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    // C/D lane map of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 r  (NOT the f32 forms' 4 (lane >> 4) + r)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + 16 * j + (lane & 15);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + 16 * w + (lane >> 4) + 4 * r;
-            if (m >= g.M || n >= g.N) continue;
-            double v = acc[j][r];
-            double* c = g.C + (long)m * g.ldc + n;
-            if (g.epi == EPI_FWD) {
-                v += (double)g.bias[n];
-                if (g.lrelu) v = v > 0.0 ? v : SLOPE * v;
-                *c = v;
-            } else if (g.epi == EPI_BWD) {
-                // the stored activation has the sign of its pre-activation (slope > 0), and a(0) = 0 takes the slope like torch's leaky_relu
-                if (g.lrelu) v *= g.mask[(long)m * g.ldm + n] > 0.0 ? 1.0 : SLOPE;
-                *c = v;
-            } else {
-                *c = g.first ? v : *c + v;
-            }
-        }
-    }
-}
+constexpr auto gemm = launch_gemm<ACT_LEAKY, RED_ACC>;      // LeakyReLU(0.2) hidden layers; weight gradients add in place, slab by slab
 
 __device__ __forceinline__ double sigmoid64(double x) { return 1.0 / (1.0 + exp(-x)); }
 
@@ -158,20 +61,6 @@ __global__ void k_latent_grad(const double* dLAT, const double* E, const float* 
     dRAW[i] = de * (1.0 - (var ? (double)var[j] : 0.0));
 }
 
-// fp64 accumulator [n_out, k_in + 1] (last column: bias) -> the parameter-shaped fp32 gradients, one rounding each
-__global__ void k_finish(const double* acc, int n_out, int k_in, float* gW, float* gb) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)n_out * (k_in + 1)) return;
-    const int o = (int)(i / (k_in + 1)), c = (int)(i % (k_in + 1));
-    if (c < k_in) {
-        if (gW) gW[(long)o * k_in + c] = (float)acc[i];
-    } else if (gb) {
-        gb[o] = (float)acc[i];
-    }
-}
-
-struct Layer { int n_out, k_in; long in_ld; };      // in_ld: row stride of the layer's input rows
-
 struct Plan {
     Layer L[8];
     long acc_off[8];          // doubles
@@ -192,7 +81,7 @@ Plan make_plan(long S, int in_dim, int od) {
         o += (long)no[l] * (ki[l] + 1);
     }
     p.acc_total = o;
-    auto take = [&](long n) { long at = o; o += (n + 7) & ~7L; return at; };
+    Take take{o};
     for (int l = 0; l < 4; ++l) p.A[l] = take(S * 512);
     p.RAW = take(S * 32);
     p.E = take(S * 32);
@@ -206,7 +95,7 @@ Plan make_plan(long S, int in_dim, int od) {
     p.dRAW = take(S * 32);
     p.dZ[0] = take(S * 512);
     p.dZ[1] = take(S * 512);
-    p.total = o;
+    p.total = take.o;
     return p;
 }
 
@@ -216,16 +105,6 @@ bool check_dims(long n, long slab_rows, int in_dim, int out_dim) {
     if (in_dim < 1 || in_dim > 64) return fail("in_dim = %d outside [1, 64]", in_dim), false;
     if (out_dim < 1 || out_dim > 16) return fail("out_dim = %d outside [1, 16]", out_dim), false;
     return true;
-}
-
-thread_local int g_launches;
-
-int launch_gemm(const Gemm& g, hipStream_t st) {
-    if (g.M <= 0 || g.N <= 0) return 0;
-    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM);
-    hipLaunchKernelGGL(k_gemm64, grid, dim3(256), 0, st, g);
-    ++g_launches;
-    return hipGetLastError() != hipSuccess;
 }
 
 }  // namespace
@@ -262,15 +141,11 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
     if (!any) return 0;
     const long S0 = n < slab_rows ? n : slab_rows;
     const Plan p = make_plan(S0, in_dim, out_dim);
-    if (!scratch) return fail("null pointer: scratch");
-    if ((uintptr_t)scratch % 8) return fail("scratch is not 8-byte aligned");
-    if (scratch_bytes < p.total * (long)sizeof(double))
-        return fail("scratch too small: %ld bytes given, %ld needed (rb_train_ae_bwd_scratch_bytes)", scratch_bytes, p.total * (long)sizeof(double));
+    if (check_scratch(scratch, scratch_bytes, p.total * (long)sizeof(double), "rb_train_ae_bwd_scratch_bytes")) return 1;
     hipStream_t st = (hipStream_t)stream;
     double* D = (double*)scratch;
     g_launches = 0;
     int bad = 0;
-    auto ew_grid = [](long items) { return dim3((unsigned)((items + 255) / 256)); };
     const bool want_layer[8] = {grads[0] || grads[1], grads[2] || grads[3], grads[4] || grads[5], grads[6] || grads[7],
                                 grads[8] || grads[9], grads[10] || grads[11], grads[12] || grads[13], grads[14] || grads[15]};
 
@@ -289,8 +164,8 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
             g.ones_col = -1;
             g.M = (int)M; g.N = L.n_out; g.K = L.k_in;
             g.epi = EPI_FWD; g.C = out[l]; g.ldc = L.n_out; g.bias = params[2 * l + 1];
-            g.lrelu = l != 4 && l != 7;
-            bad |= launch_gemm(g, st);
+            g.act = l != 4 && l != 7;
+            bad |= gemm(g, 1, st);
         };
         // d loss / d (pre-activation of layer l) sits in dz [M, n_out]: accumulate dW | db, and (to != NULL) hand the gradient to layer l - 1
         auto backward = [&](int l, long M, const double* dz, double* to, bool mask_prev) {
@@ -301,8 +176,8 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
                 g.B = in[l]; g.sbk = L.in_ld; g.sbn = 1; g.b_f32 = l == 0;          // B(k = row, n = input column)
                 g.ones_col = L.k_in;
                 g.M = L.n_out; g.N = L.k_in + 1; g.K = (int)M;
-                g.epi = EPI_ACC; g.C = D + p.acc_off[l]; g.ldc = L.k_in + 1; g.first = first;
-                bad |= launch_gemm(g, st);
+                g.epi = EPI_WGRAD; g.C = D + p.acc_off[l]; g.ldc = L.k_in + 1; g.first = first;
+                bad |= gemm(g, 1, st);
             }
             if (to) {
                 Gemm g{};
@@ -311,8 +186,8 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
                 g.ones_col = -1;
                 g.M = (int)M; g.N = L.k_in; g.K = L.n_out;
                 g.epi = EPI_BWD; g.C = to; g.ldc = L.k_in;
-                g.lrelu = mask_prev; g.mask = (const double*)in[l]; g.ldm = L.in_ld;
-                bad |= launch_gemm(g, st);
+                g.act = mask_prev; g.mask = (const double*)in[l]; g.ldm = L.in_ld;
+                bad |= gemm(g, 1, st);
             }
         };
         for (int l = 0; l < 5; ++l) forward(l, S);
@@ -343,13 +218,7 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
         }
         if (stats) stats[1] = 1;
     }
-    for (int l = 0; l < 8; ++l) {
-        if (!want_layer[l]) continue;
-        const Layer& L = p.L[l];
-        hipLaunchKernelGGL(k_finish, ew_grid((long)L.n_out * (L.k_in + 1)), dim3(256), 0, st, D + p.acc_off[l], L.n_out, L.k_in,
-                           grads[2 * l], grads[2 * l + 1]);
-        ++g_launches;
-    }
+    finish_layers(p.L, 8, D, p.acc_off, grads, st);
     if (stats) stats[0] = g_launches;
     if (bad || hipGetLastError() != hipSuccess) return fail("kernel launch failed");
     return 0;

@@ -475,25 +475,38 @@ def ae_backward(X, params, g_out=None, g_out_xi=None, g_raw=None, noise=None, va
     opt = lambda t, cols: None if t is None else _f32(t.detach()).reshape(n, cols)
     g_out, g_out_xi, g_raw, noise = opt(g_out, out_dim), opt(g_out_xi, out_dim), opt(g_raw, 32), opt(noise, 32)
     var = None if var is None else _f32(var.detach()).reshape(32)
-    unknown = set(want) - set(AE_PARAM_NAMES)
-    if unknown:
-        raise KeyError(f"ae_backward: no such parameter: {sorted(unknown)}")
-    alloc = torch.zeros if n == 0 else torch.empty           # n > 0: k_finish stores every element of every wanted gradient
-    out = {k: alloc(p.shape, dtype=torch.float32, device=dev) for k, p in zip(AE_PARAM_NAMES, params) if k in want}
     slab = int(slab_rows or AE_SLAB_ROWS)
     stats = (c_int * 2)(0, 0)
-    nbytes = 0
-    if n > 0 and out:
-        nbytes = int(_lib.train().rb_train_ae_bwd_scratch_bytes(c_long(n), c_long(slab), c_int(in_dim), c_int(out_dim)))
-        if nbytes < 0:
-            raise _lib.RobirHipError("rb_train_ae_bwd_scratch_bytes: " + _lib.train().rb_train_last_error().decode())
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        P = (ctypes.c_void_p * 16)(*[p.data_ptr() for p in params])
-        G = (ctypes.c_void_p * 16)(*[out[k].data_ptr() if k in out else None for k in AE_PARAM_NAMES])
-        _lib.call_train("rb_train_ae_bwd", ptr(X), c_long(n), c_int(in_dim), ptr(noise), ctypes.c_double(noise_scale), ptr(var),
-                        c_int(latent_act), c_int(1 if sigmoid_out else 0), c_int(out_dim), P, ptr(g_out), ptr(g_out_xi), ptr(g_raw), G,
-                        c_long(slab), ptr(scratch), c_long(nbytes), stats, stream_ptr())
+    out, nbytes = _param_backward(
+        "ae_backward", AE_PARAM_NAMES, params, want, rows=n, dev=dev, lib=_lib.train, query="rb_train_ae_bwd_scratch_bytes",
+        query_args=(c_long(n), c_long(slab), c_int(in_dim), c_int(out_dim)),
+        launch=lambda P, G, scratch, nbytes: _lib.call_train(
+            "rb_train_ae_bwd", ptr(X), c_long(n), c_int(in_dim), ptr(noise), ctypes.c_double(noise_scale), ptr(var), c_int(latent_act),
+            c_int(1 if sigmoid_out else 0), c_int(out_dim), P, ptr(g_out), ptr(g_out_xi), ptr(g_raw), G, c_long(slab), ptr(scratch),
+            c_long(nbytes), stats, stream_ptr()))
     return out, {"launches": int(stats[0]), "encoder_pass": bool(stats[1]), "scratch_bytes": nbytes}
+
+
+def _param_backward(who, names, params, want, *, rows, dev, lib, query, query_args, launch):
+    """The common tail of ae_backward / vis_backward (`who`, for the error text): allocates the gradients named in `want` (a subset of
+    `names`, the order of `params`) and -- rows > 0 and something wanted -- the fp64 scratch that lib()'s `query` asks for, then runs
+    launch(params' pointer array, gradients' pointer array with NULL for the unwanted, scratch, its bytes).  -> (dict name -> gradient,
+    scratch bytes)."""
+    unknown = set(want) - set(names)
+    if unknown:
+        raise KeyError(f"{who}: no such parameter: {sorted(unknown)}")
+    alloc = torch.zeros if rows == 0 else torch.empty           # rows > 0: k_finish stores every element of every wanted gradient
+    out = {k: alloc(p.shape, dtype=torch.float32, device=dev) for k, p in zip(names, params) if k in want}
+    nbytes = 0
+    if rows > 0 and out:
+        nbytes = int(getattr(lib(), query)(*query_args))
+        if nbytes < 0:
+            raise _lib.RobirHipError(f"{query}: " + _lib.aux_error(lib()))
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        P = (ctypes.c_void_p * len(names))(*[p.data_ptr() for p in params])
+        G = (ctypes.c_void_p * len(names))(*[out[k].data_ptr() if k in out else None for k in names])
+        launch(P, G, scratch, nbytes)
+    return out, nbytes
 
 
 VIS_PARAM_NAMES = tuple(f"vis_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias"))
@@ -514,25 +527,15 @@ def vis_backward(points, dirs, rep, params, g_logits, want=VIS_PARAM_NAMES, slab
     assert dirs.dim() == 2 and dirs.shape[1] == 3 and rep >= 1 and points.shape[0] * rep == M and len(params) == 10
     params = [_f32(p.detach()) for p in params]
     g_logits = _f32(g_logits.detach()).reshape(M, 2)
-    unknown = set(want) - set(VIS_PARAM_NAMES)
-    if unknown:
-        raise KeyError(f"vis_backward: no such parameter: {sorted(unknown)}")
-    alloc = torch.zeros if M == 0 else torch.empty           # M > 0: k_finish stores every element of every wanted gradient
-    out = {k: alloc(p.shape, dtype=torch.float32, device=dev) for k, p in zip(VIS_PARAM_NAMES, params) if k in want}
     slab = int(slab_rows or VIS_SLAB_ROWS)
     part = int(part_rows or min(slab, VIS_PART_ROWS))
     stats = (c_int * 3)(0, 5, 0)
-    nbytes = 0
-    if M > 0 and out:
-        L = _lib.vistrain()
-        nbytes = int(L.rb_vt_vis_bwd_scratch_bytes(c_long(M), c_long(slab), c_long(part)))
-        if nbytes < 0:
-            raise _lib.RobirHipError("rb_vt_vis_bwd_scratch_bytes: " + L.rb_vt_last_error().decode())
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        P = (ctypes.c_void_p * 10)(*[p.data_ptr() for p in params])
-        G = (ctypes.c_void_p * 10)(*[out[k].data_ptr() if k in out else None for k in VIS_PARAM_NAMES])
-        _lib.call_vistrain("rb_vt_vis_bwd", ptr(points), ptr(dirs), c_long(M), c_int(rep), P, ptr(g_logits), G, c_long(slab), c_long(part),
-                           ptr(scratch), c_long(nbytes), stats, stream_ptr())
+    out, nbytes = _param_backward(
+        "vis_backward", VIS_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.vistrain, query="rb_vt_vis_bwd_scratch_bytes",
+        query_args=(c_long(M), c_long(slab), c_long(part)),
+        launch=lambda P, G, scratch, nbytes: _lib.call_vistrain(
+            "rb_vt_vis_bwd", ptr(points), ptr(dirs), c_long(M), c_int(rep), P, ptr(g_logits), G, c_long(slab), c_long(part), ptr(scratch),
+            c_long(nbytes), stats, stream_ptr()))
     return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
 
 

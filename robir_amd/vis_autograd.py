@@ -7,20 +7,10 @@ visibility-training library, which recomputes the encoding and every activation 
 ctx.needs_input_grad turns into NULL pointers."""
 import torch
 
-from . import ops
+from . import ops, param_autograd
 
 SLAB_ROWS = ops.VIS_SLAB_ROWS      # rows per slab of the backward (bounds its scratch independently of M); tests use small values
 PART_ROWS = ops.VIS_PART_ROWS      # rows per partition of a weight gradient's row range inside a slab
-
-
-def refuse_input_grad(**tensors):
-    """points / directions are not differentiable on this path: say so instead of returning a zero gradient."""
-    if not torch.is_grad_enabled():
-        return
-    for name, t in tensors.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"robir_amd visibility network has no gradient with respect to `{name}` (its HIP backward differentiates the "
-                                      f"network parameters only: pass {name}.detach(), or differentiate the input on the reference's modules)")
 
 
 def linear_params(net):
@@ -29,10 +19,7 @@ def linear_params(net):
 
 
 class VisLogitsFn(torch.autograd.Function):
-    """Saved through ctx.save_for_backward, and nothing else: the points, the directions and the parameters -- no activation, no output.
-    Tensors never sit on ctx as plain attributes (output -> grad_fn -> ctx -> output would be a reference cycle that only the cyclic
-    collector frees; autograd checks saved inputs for in-place changes -- an optimiser step between forward and backward is an error, not
-    a silently stale gradient).  ctx keeps the module-independent scalars."""
+    """Saves the points, the directions and the parameters (param_autograd: what is saved, and why that way)."""
 
     @staticmethod
     def forward(ctx, net, points, dirs, rep, *params):
@@ -54,10 +41,10 @@ class VisLogitsFn(torch.autograd.Function):
             return (None,) * (4 + len(params))
         grads, _ = ops.vis_backward(points, dirs, rep, params, g_logits.float().contiguous(), want=want, slab_rows=slab,
                                     part_rows=part or min(slab, PART_ROWS))
-        return (None, None, None, None, *(grads[k].to(p.dtype) if k in grads else None for k, p in zip(ops.VIS_PARAM_NAMES, params)))
+        return param_autograd.backward_result(4, ops.VIS_PARAM_NAMES, params, grads)
 
 
 def logits(net, points, dirs, rep=1):
     """VisNetwork.logits_from_points with a graph to the network's parameters: points [M/rep,3], dirs [M,3] -> logits [M,2]."""
-    refuse_input_grad(points=points, dirs=dirs)
+    param_autograd.refuse_input_grad("visibility network", points=points, dirs=dirs)
     return VisLogitsFn.apply(net, points, dirs, int(rep), *linear_params(net))
