@@ -23,6 +23,19 @@
   ROBIR_PRECISION=f16-vis           round 4's meaning of `f16`, kept selectable: plain f16 for the light-visibility MLP only,
                                     every other net on the exact-operand kernels -- needs the default library only.
 ROBIR_VIS_PRECISION / ROBIR_MLP_PRECISION override the two halves of the policy separately (A/B runs, tests).
+
+Operand range of `exact` (tests/split_model.py holds the constants, tests/test_split_cpu.py establishes them on a numpy restatement of the
+splits, tests/test_mlp_gpu.py and tests/test_precision_gpu.py hold the device to them; DESIGN section 6 has the measurements):
+  six f16 products (every stand-alone f16x6 kernel; f16x6-1t)   a weight or activation v is carried EXACTLY as h + m 2^-11 + l 2^-22 for
+                                    2^-23 <= |v| <= 65504 (EXACT_MIN, F16_MAX) and for +-0 -- f16 subnormals included, and through the binade
+                                    [32768, 65504) where the m piece of an activation relies on the round-toward-zero clamp at 65504.
+                                    Below 2^-23 the absolute error is at most min(|v|, 2^-47) (BELOW_WINDOW_ABS_ERR = 7.1e-15).  From
+                                    65504 on the leading piece saturates and ops.range_check reports the kernel (packing refuses such weights).
+  bf8 form (the shipped light-visibility kernel, f16x6-pt / f16x6-stream: h.xl and l.xh from e5m2 copies)   the copy of the third piece is
+                                    bit-exact for 2^-15 <= |v| <= 65504 (BF8_L_EXACT_MIN; the first magnitude that fails is one fp32 unit
+                                    below 2^-15, BF8_L_FIRST_FAIL): there l has at most three significant bits.  Below 2^-15 the operand
+                                    is off by less than 2^-38 in absolute terms (BF8_BELOW_WINDOW_ABS_ERR = 3.6e-12): still fp32-like
+                                    for typical activations down to ~2^-17, past the 1e-4 bar once they fall to ~2^-25.
 """
 import os
 

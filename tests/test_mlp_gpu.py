@@ -829,3 +829,73 @@ def test_cesr_exact_operand_kernels(dev):
             assert float((a - ref).abs().max()) <= 5e-6 * scale, ("shadow_net", n, nl, float((a - ref).abs().max()), scale)
             assert torch.equal(a, ops.cesr_net_x6_points(p, n * nl, 2, sh6, nl)), (n, nl)
     ops.range_check(sync=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the exact-operand packing on the device against its numpy restatement (tests/split_model.py; tests/test_split_cpu.py holds the model's own
+# properties): every half of the blob, bit for bit
+@pytest.mark.parametrize("scale_log2", [0, 8])
+@pytest.mark.parametrize("with_perm", [False, True])
+def test_pack_layer_x6_bit_for_bit(dev, scale_log2, with_perm):
+    """rb_pack_layer_x6 over ragged shapes (n_out 1 / 17 / 256 in n_pad = the next multiple of 16; k_in 3 / 39 / 63 / 191 / 256 in k_pad = the
+    next multiple of 32), with and without bias, weights over every binade from fp32 subnormals to just under 65504 2^-s plus +-0: piece
+    order, k-block -> column map, perm (with -1 and out-of-range entries), zero halves in padding rows and columns, biases b 2^s, and the
+    three roundings of every weight -- f16 subnormals included: the device must carry them like the model does."""
+    import split_model as sm
+    from robir_amd import packing
+    rng = np.random.default_rng(1000 + 10 * scale_log2 + int(with_perm))
+    for n_out in (1, 17, 256):
+        for k_in in (3, 39, 63, 191, 256):
+            n_pad, k_pad = (n_out + 15) // 16 * 16, (k_in + 31) // 32 * 32
+            W = sm.operand_matrix(rng, n_out, k_in, top=sm.F16_MAX * 2.0 ** -scale_log2)
+            perm = None
+            if with_perm:                                         # a shuffle of the columns with holes: -1, other negatives, k_in and beyond
+                perm = rng.permutation(k_pad + 8)[:k_pad].astype(np.int64) - 4
+                perm[rng.integers(0, k_pad)] = -1
+                perm[rng.integers(0, k_pad)] = k_in
+                perm[rng.integers(0, k_pad)] = 2 ** 31 - 1
+            for with_bias in (False, True):
+                b = (rng.standard_normal(n_out) * 10.0 ** rng.integers(-30, 30, n_out)).astype(np.float32) if with_bias else None
+                layer = dict(W=torch.from_numpy(W), b=None if b is None else torch.from_numpy(b), n_pad=n_pad, k_pad=k_pad,
+                             perm=None if perm is None else perm.tolist())
+                got = packing.pack_layers_x6([layer], dev, scale_log2=scale_log2).cpu().numpy()
+                want = sm.pack_layer_x6(W, b, n_pad, k_pad, perm, scale_log2)
+                assert got.shape == want.shape, (n_out, k_in, with_bias)
+                g16, w16 = got.view(np.uint16), want.view(np.uint16)
+                if not np.array_equal(g16, w16):
+                    i = int(np.nonzero(g16 != w16)[0][0])
+                    is_bias, row, k, piece = (a[i] for a in sm.layout_x6(n_pad, k_pad))
+                    raise AssertionError(("first differing half", n_out, k_in, with_bias, i, bool(is_bias), int(row), int(k), int(piece),
+                                          hex(g16[i]), hex(w16[i]), int((g16 != w16).sum())))
+                # stated on its own: padding is zero halves, the biases are b 2^s
+                is_bias, row, k, piece = sm.layout_x6(n_pad, k_pad)
+                col = k if perm is None else np.where(k >= 0, perm[np.maximum(k, 0)], -1)
+                pad = ~is_bias & ((row >= n_out) | (col < 0) | (col >= k_in))
+                assert pad.any() or (n_out == n_pad and k_in == k_pad and perm is None)
+                assert not g16[pad].any()
+                bias = got[sm.bias_index(np.arange(n_pad), k_pad)]
+                want_b = np.zeros(n_pad, np.float32)
+                if with_bias:
+                    with np.errstate(over="ignore"):
+                        want_b[:n_out] = b * np.float32(2.0 ** scale_log2)
+                assert np.array_equal(bias.view(np.uint32), want_b.view(np.uint32))
+
+
+def test_vis_split_fp8_blob_bit_for_bit(dev):
+    """pack_vis_split(...)["hidden_x6_head_fp8"] -- the 49 chunks the default light-visibility kernel streams -- against the model: the device's
+    three-piece packing of the three hidden layers and the head, then the model's bf8 re-arrangement.  Weights over the whole operand range."""
+    import split_model as sm
+    from robir_amd import packing
+    rng = np.random.default_rng(77)
+    shapes = {0: (256, 126), 2: (256, 256), 4: (256, 256), 6: (256, 256), 8: (2, 256)}
+    sd = {}
+    for l, (n, k) in shapes.items():
+        sd[packing.VIS + "%d.weight" % l] = sm.operand_matrix(rng, n, k)
+        sd[packing.VIS + "%d.bias" % l] = rng.standard_normal(n).astype(np.float32)
+    split = packing.pack_vis_split(sd, dev)
+    model = np.concatenate([sm.pack_layer_x6(sd[packing.VIS + "%d.weight" % l], sd[packing.VIS + "%d.bias" % l], 256 if l < 8 else 16, 256)
+                            for l in (2, 4, 6, 8)])
+    got6 = split["hidden_x6_head"].cpu().numpy()
+    assert np.array_equal(got6.view(np.uint32), model.view(np.uint32))
+    got8 = split["hidden_x6_head_fp8"].cpu().numpy()
+    assert np.array_equal(got8.view(np.uint32), sm.repack_fp8(model, ((256, 49),)).view(np.uint32))

@@ -250,15 +250,17 @@ def _f64(sd):
     return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
 
 
-def _per_net_cases(dev, sd_np):
-    """[(name, oracle(sd, dtype) -> tensor, {form: thunk -> device tensor})]: inputs are drawn once (fp32) and shared by every column."""
+def _per_net_cases(dev, sd_np, x=None, n=PER_NET_ROWS, cesr_seed=0):
+    """[(name, oracle(sd, dtype) -> tensor, {form: thunk -> device tensor})]: inputs are drawn once (fp32) and shared by every column.
+    x: the points [n,3] (default: n stage-2 points around the object); n: the row count, a multiple of 8."""
     from robir_amd import ops, packing, synth
     from robir_oracle import nets as on
     from robir_oracle.encoding import pe
     import torch.nn.functional as F
     g = torch.Generator().manual_seed(20260929)
-    n = PER_NET_ROWS
-    x = (torch.rand(n, 3, generator=g) - 0.5) * 1.2                                      # stage-2 points around the object
+    if x is None:
+        x = (torch.rand(n, 3, generator=g) - 0.5) * 1.2                                  # stage-2 points around the object
+    assert x.shape == (n, 3) and x.dtype == torch.float32 and n % 8 == 0
     view = F.normalize(torch.randn(n, 3, generator=g), dim=-1)
     nrm = F.normalize(torch.randn(n, 3, generator=g), dim=-1)
     hdr = torch.rand(n, 1, generator=g)
@@ -274,7 +276,7 @@ def _per_net_cases(dev, sd_np):
     pre = "envmap_material_network.spec_brdf_encoder_layer"
     enc32, _ = packing.pack_sparse_ae(sd_np, pre, dev)
     enc6 = packing.pack_sparse_ae_encoder_x6(sd_np, pre, dev)
-    cesr = synth.synth_cesr_nets(0)
+    cesr = synth.synth_cesr_nets(cesr_seed)
     no = {"net." + k: v for k, v in cesr["normal_net"].items()}
     sh = {"net." + k: v for k, v in cesr["shadow_net"].items()}
     no32, no6 = packing.pack_softplus512(no, "net.", 63, dev), packing.pack_softplus512_x6(no, "net.", 63, dev)
@@ -370,3 +372,330 @@ def test_per_net_error_budget(weights):
                 assert st[c + q] <= PER_NET_VS_K32 * st["k32" + q] + ulp, (name, c, q, "vs f32-input MFMA", st)
                 assert st[c + q] <= PER_NET_VS_O32 * st["o32" + q] + ulp, (name, c, q, "vs the reference's fp32", st)
             assert st[c + "_p99"] <= 1e-4 and st[c + "_max"] <= 1e-4 * 4, (name, c, st)      # and north_star's bar itself
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the same rule over the OPERAND RANGE of the exact-operand kernels (tests/split_model.py states the windows, tests/test_split_cpu.py
+# establishes them on paper): the ray-march input domain with its special points, more weight draws, and -- for the positively homogeneous
+# nets -- hidden activations moved by exact powers of two up to the clamp's binade and down through the f16 subnormals.
+DOMAIN_ROWS = 1024           # 2048 entries for the two-output nets: the 99th percentile is the ~20th largest entry
+
+
+def _domain_points(n, seed):
+    """n points: uniform in [-1.5, 1.5]^3 (the ray-march range; with in_scale = 2 the encoding's arguments reach 2^9 * 3 = 1536) and a block of
+    special rows: the origin, -0.0, the eight +-1 corners, axis-aligned points, points with one coordinate of +-2^-30."""
+    t = 2.0 ** -30
+    special = [[0.0, 0.0, 0.0], [-0.0, -0.0, -0.0]]
+    special += [[a, b, c] for a in (-1.0, 1.0) for b in (-1.0, 1.0) for c in (-1.0, 1.0)]
+    for axis in range(3):
+        for v in (-1.5, -0.37, 0.5, 1.0):
+            special.append([v if i == axis else 0.0 for i in range(3)])
+        for v in (-t, t):
+            special.append([v if i == axis else (0.3, -0.7, 0.45)[i] for i in range(3)])
+    special = torch.tensor(special, dtype=torch.float32)
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(n - special.shape[0], 3, generator=g) - 0.5) * 3.0
+    return torch.cat([x, special])
+
+
+def _quantiles(v, ref):
+    e = err_entries(v, ref)
+    return {"p50": float(e.quantile(0.5)), "p99": float(e.quantile(0.99)), "max": float(e.max())}
+
+
+def _rule_violations(st, col):
+    """the project's rule for column `col` of st[column][quantile] on the median and the 99th percentile; -> list of violations"""
+    ulp, bad = 2.0 ** -23, []
+    for q in ("p50", "p99"):
+        if not st[col][q] <= PER_NET_VS_K32 * st["k32"][q] + ulp:
+            bad.append((col, q, "vs f32-input MFMA", st[col][q], st["k32"][q]))
+        if not st[col][q] <= PER_NET_VS_O32 * st["o32"][q] + ulp:
+            bad.append((col, q, "vs the reference's fp32", st[col][q], st["o32"][q]))
+    return bad
+
+
+def _flat(st):
+    return {f"{c}_{q}": v for c, d in st.items() for q, v in d.items()}
+
+
+@pytest.mark.parametrize("weights", ["init", "trained_like"])
+@pytest.mark.parametrize("seed", [0, 3, 11])
+def test_per_net_error_budget_ray_march_domain(seed, weights):
+    """test_per_net_error_budget's rule (same constants, same float64 anchor, all eight nets + the SDF gradient, both tile forms) on the input
+    domain the ray march really covers -- points in [-1.5, 1.5]^3 plus the special rows of _domain_points -- and on three weight draws, each as
+    drawn and trained-like.  DOMAIN_ROWS rows: the smallest count that keeps the 99th percentile over ~2000 entries for the two-output nets."""
+    import importlib
+    from robir_amd import ops, synth
+    from robir_oracle import nets as on
+    dev = torch.device("cuda:0")
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    sd_np = synth.synth_state_dict(seed, variance=0.3)
+    if weights == "trained_like":
+        sd_np = importlib.import_module("test_mlp_gpu")._trained_like(sd_np, 5 + seed)
+    sd32 = on.as_torch(sd_np)
+    sd64 = _f64(sd32)
+    x = _domain_points(DOMAIN_ROWS, 700 + seed)
+    ops.range_check(sync=True)
+    bad = []
+    for name, oracle, forms in _per_net_cases(dev, sd_np, x=x, n=DOMAIN_ROWS, cesr_seed=seed):
+        r64, o32 = oracle(sd64, torch.float64), oracle(sd32, torch.float32)
+        assert o32.dtype == torch.float32 and r64.dtype == torch.float64, name
+        st = {"o32": _quantiles(o32, r64)}
+        for form, thunk in forms.items():
+            st[form] = _quantiles(thunk().cpu().reshape(r64.shape), r64)
+        record_metric(f"per_net_error_budget_domain/seed{seed}/{weights}/{name}", entries=int(r64.numel()), **_flat(st))
+        print(f"{name:20s} " + "  ".join(f"{c}: p50 {d['p50']:.2e} p99 {d['p99']:.2e} max {d['max']:.2e}" for c, d in st.items()))
+        for c in st:
+            if c.startswith("x6"):
+                bad += [(name,) + b for b in _rule_violations(st, c)]
+                if not (st[c]["p99"] <= 1e-4 and st[c]["max"] <= 4e-4):
+                    bad.append((name, c, "north_star's bar", st[c]["p99"], st[c]["max"]))
+    ops.range_check(sync=True)
+    assert not bad, bad
+
+
+# ---- power-of-two regimes ----------------------------------------------------------------------------------------------------
+# A ReLU / LeakyReLU net is positively homogeneous: the first layer's weight and every bias times 2^k moves ALL hidden activations by 2^k
+# exactly (a power of two: no rounding in fp32 or float64 short of under- / overflow), and the outputs with them.  The error measure
+# |a - b| / (|b| + mean|b|) does not see the factor, so the rule applies as it stands.  Regimes are named by where they put the float64
+# oracle's hidden activations on the test's inputs:
+#   hot        the LARGEST in [32752, 65504): the binade in which sx_split_pair's m piece relies on the round-toward-zero clamp; with k + 1 the
+#              largest is >= 65504 and the range sentinel must report
+#   bf8_edge   the MEDIAN non-zero magnitude in [2^-15, 2^-14): the lowest binade in which the bf8 copy of the third piece is still exact
+#   cold       ... in [2^-17, 2^-16): h pieces are f16 subnormals, every piece still inside the exact window (>= 2^-23 but for the ~1 % of
+#              activations more than 2^6 below the median, whose absolute error is <= 2^-47): INSIDE the six-product window, BELOW the bf8 form's
+#   below      ... in [2^-27, 2^-26): below both windows; an operand is then off by <= 2^-47, ~2^-21 of the median: recorded, held to the 1e-4 bar
+def _hidden_magnitudes(weights, h, act, stride=1):
+    """float64 hidden activations of a 4-hidden-layer net on rows h: ([largest magnitude of each layer], [median non-zero magnitude of each
+    layer, over every `stride`-th row])"""
+    import torch.nn.functional as F
+    mx, med = [], []
+    for W, b in weights[:4]:
+        h = act(F.linear(h, W.double(), b.double()))
+        a = h.abs()
+        mx.append(float(a.max()))
+        a = a[::stride]
+        med.append(float(a[a > 0].median()))
+    return mx, med
+
+
+def _k_into(value, lo):
+    """the k with lo <= value 2^k < 2 lo"""
+    import math
+    k = math.floor(math.log2(lo / value))
+    while value * 2.0 ** k < lo:
+        k += 1
+    while value * 2.0 ** k >= 2 * lo:
+        k -= 1
+    return k
+
+
+def _regime_ks(mx, med):
+    from split_model import BF8_L_EXACT_MIN
+    return {"base": 0, "hot": _k_into(mx, 32752.0), "bf8_edge": _k_into(med, BF8_L_EXACT_MIN), "cold": _k_into(med, 2.0 ** -17),
+            "below": _k_into(med, 2.0 ** -27)}
+
+
+def _pow2_regime(sd_np, prefix, k, k3=None, head_k=0):
+    """layers prefix + '0' .. '8' with the activations of hidden layers 0-2 moved by 2^k, those of hidden layer 3 by 2^k3 (default: k too) and
+    the outputs by 2^(k3 + head_k): first weight times 2^k, layer 3's times 2^(k3 - k), the output layer's times 2^head_k, every bias by
+    its layer's factor.  Powers of two: nothing is rounded."""
+    k3 = k if k3 is None else k3
+    out = dict(sd_np)
+    for key, e in (("0.weight", k), ("0.bias", k), ("2.bias", k), ("4.bias", k), ("6.weight", k3 - k), ("6.bias", k3), ("8.weight", head_k),
+                   ("8.bias", k3 + head_k)):
+        out[prefix + key] = sd_np[prefix + key] * np.float32(2.0 ** e)
+        assert np.array_equal(out[prefix + key].astype(np.float64), sd_np[prefix + key].astype(np.float64) * 2.0 ** e), (key, e)      # nothing flushed
+    return out
+
+
+def _homogeneous_nets(dev, x, view, hdr):
+    """{name: (weight prefix, activation, feature rows (float64), sentinel's name for the kernel, k32 thunk(sd), x6 thunk(sd), oracle(sd, dtype))}"""
+    from robir_amd import ops, packing
+    from robir_oracle import nets as on
+    from robir_oracle.encoding import pe
+    import torch.nn.functional as F
+    xd, vd, hd = x.to(dev), view.to(dev), hdr.to(dev)
+    pre = "envmap_material_network.spec_brdf_encoder_layer"
+    lrelu = lambda t: F.leaky_relu(t, 0.2)
+    xh = x * 0.5
+    return {
+        "visibility_logits": (on.VIS, torch.relu, torch.cat([pe(xh.double(), 10), pe(view.double(), 10)], -1), "rb_vis_x6_points",
+                              lambda sd: ops.vis_mlp_points(xd * 0.5, vd, packing.pack_vis(sd, dev), 1),
+                              lambda sd: ops.vis_x6_points(xd * 0.5, vd, packing.pack_vis_x6(sd, dev), 1),
+                              lambda sd, dt: on.vis_logits(sd, xh.to(dt), view.to(dt))),
+        "illum_lobe_net_512": (on.ILL + "lobe_layer.", torch.relu, torch.cat([pe(xh.double(), 10), hdr.double()], -1), "rb_wide_x6",
+                               lambda sd: ops.wide_mlp_points(xd * 0.5, hd, packing.pack_illum(sd, dev), False),
+                               lambda sd: ops.wide_x6_points(xd * 0.5, hd, packing.pack_illum_x6(sd, dev), False),
+                               lambda sd, dt: on._seq(sd, on.ILL + "lobe_layer.", 5, torch.cat([pe(xh.to(dt), 10), hdr.to(dt)], -1), torch.relu)),
+        "spec_encoder_512": (pre + ".brdf_encoder_layer.", lrelu, pe(xh.double(), 10), "rb_wide_x6",
+                             lambda sd: ops.wide_mlp_points(xd * 0.5, None, packing.pack_sparse_ae(sd, pre, dev)[0], True),
+                             lambda sd: ops.wide_x6_points(xd * 0.5, None, packing.pack_sparse_ae_encoder_x6(sd, pre, dev), True),
+                             lambda sd, dt: on._seq(sd, pre + ".brdf_encoder_layer.", 5, pe(xh.to(dt), 10), lrelu)),
+    }
+
+
+@pytest.mark.parametrize("net", ["visibility_logits", "illum_lobe_net_512", "spec_encoder_512"])
+def test_error_budget_power_of_two_regimes(net):
+    """The stand-alone six-product kernels of the positively homogeneous nets with their hidden activations moved by exact powers of two
+    (regimes above).  Per regime: the f32-input-MFMA result is the base result times 2^k bit for bit (else fp32 itself under- or overflowed and
+    the regime measures nothing); hot / bf8_edge / cold are inside the exact window: the rule holds and the sentinel stays silent; hot + 1 is
+    reported by the sentinel with the kernel's name; below: the quantiles are recorded and held to the 1e-4 / 4e-4 bar, run-to-run bit-identical."""
+    import torch.nn.functional as F
+    from robir_amd import ops, synth, _lib
+    from robir_oracle import nets as on
+    dev = torch.device("cuda:0")
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    sd_np = synth.synth_state_dict(0, variance=0.3)
+    n = DOMAIN_ROWS
+    g = torch.Generator().manual_seed(4242)
+    x = _domain_points(n, 900)
+    view = F.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    hdr = torch.rand(n, 1, generator=g)
+    prefix, act, rows, kernel_name, k32_of, x6_of, oracle = _homogeneous_nets(dev, x, view, hdr)[net]
+    base64 = _f64(on.as_torch(sd_np))
+    mxs, meds = _hidden_magnitudes([(base64[prefix + "%d.weight" % (2 * i)], base64[prefix + "%d.bias" % (2 * i)]) for i in range(5)], rows, act)
+    mx, med = max(mxs), float(np.median(meds))
+    ks = _regime_ks(mx, med)
+    assert 32752.0 <= mx * 2.0 ** ks["hot"] < 65504.0 and ks["hot"] > 0 > ks["bf8_edge"] > ks["cold"] > ks["below"], (mx, med, ks)
+    ops.range_check(sync=True)
+    k32_base, bad = None, []
+    for regime, k in ks.items():
+        sd = _pow2_regime(sd_np, prefix, k)
+        sd32 = on.as_torch(sd)
+        r64, o32 = oracle(_f64(sd32), torch.float64), oracle(sd32, torch.float32)
+        k32 = k32_of(sd).cpu()
+        if regime == "base":
+            k32_base, r64_base = k32, r64
+        assert torch.equal(k32, k32_base * 2.0 ** k), (net, regime, k, "fp32 itself left its range: the regime measures nothing")
+        assert torch.equal(r64, r64_base * 2.0 ** k), (net, regime, k)
+        a = x6_of(sd)
+        ops.range_check(sync=True)                                   # every regime is inside the f16 range of the leading piece
+        st = {"o32": _quantiles(o32, r64), "k32": _quantiles(k32, r64), "x6": _quantiles(a.cpu(), r64)}
+        record_metric(f"pow2_regimes/{net}/{regime}", k=k, largest_hidden=mx * 2.0 ** k, median_hidden=med * 2.0 ** k, entries=int(r64.numel()), **_flat(st))
+        print(f"{net} {regime:9s} k {k:4d}  " + "  ".join(f"{c}: p50 {d['p50']:.2e} p99 {d['p99']:.2e} max {d['max']:.2e}" for c, d in st.items()))
+        if regime == "below":
+            assert torch.equal(a, x6_of(sd)), (net, regime)
+            if not (st["x6"]["p99"] <= 1e-4 and st["x6"]["max"] <= 4e-4):
+                bad.append((regime, "bar", st["x6"]))
+        else:
+            bad += [(regime,) + b for b in _rule_violations(st, "x6")]
+    x6_of(_pow2_regime(sd_np, prefix, ks["hot"] + 1))                # the largest activation is now in [65504, 131008): the tight side of the boundary
+    with pytest.raises(_lib.RobirHipError, match="overflowed its activation range") as ei:
+        ops.range_check(sync=True)
+    assert kernel_name in str(ei.value), str(ei.value)
+    ops.range_check(sync=True)                                       # reading cleared the words
+    assert not bad, bad
+
+
+def _head_split(k):
+    """fused kernel: how 2^-k is taken back behind hidden layers 0-2 so that the logits stay those of the base weights: the output layer's
+    weights take what keeps them inside the f16 range and the bf8 window (2^-6 .. 2^14), hidden layer 3's weights the rest.  -> (k3, head_k)"""
+    k3 = min(max(k, -14), 6)
+    return k3, -k3
+
+
+def test_light_visibility_power_of_two_regimes(monkeypatch):
+    """The fused light-visibility kernel through get_diffuse_visibility in the forms that ship -- f16x6-pt and f16x6-stream (bf8 weight layout: two
+    of the six products from bf8 copies) and, when the legacy library loads, f16x6-1t (six f16 products) -- with the hidden activations of the
+    visibility MLP moved by exact powers of two.  The visibility is a soft-max of the logits, which is NOT homogeneous, so here 2^-k is taken
+    back (powers of two again, _head_split): the activations that enter the three 256 x 256 layers -- hidden layers 0-2 -- sit in the regime,
+    the output layer's input at most 2^14 down / 2^6 up, and logits, visibilities and both oracles are those of the base weights bit for bit;
+    so must the f32-input-MFMA kernel's be (the harness check).  Rule inside a form's window (six products: hot, bf8_edge, cold; bf8: hot,
+    bf8_edge); in the first regime below it (six products: below; bf8: cold) the 1e-4 / 4e-4 bar, and run-to-run bit-identity wherever a form is
+    below its window, every quantile recorded; hot + 1 is reported by the sentinel."""
+    from robir_amd import _lib, nets, ops, sg_render, synth
+    from robir_oracle import nets as on
+    from robir_oracle.encoding import pe
+    dev = torch.device("cuda:0")
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    sd_np = {k: v for k, v in synth.synth_state_dict(0, variance=0.3).items() if k.startswith("visibility_network.")}
+    g = np.random.Generator(np.random.PCG64(62))
+    n, L, nsamp = 64, 128, 32
+    pts = torch.from_numpy((g.standard_normal((n, 3)) * 0.25).astype(np.float32))
+    nrm = torch.nn.functional.normalize(torch.from_numpy(g.standard_normal((n, 3)).astype(np.float32)), dim=-1)
+    lgt = torch.from_numpy(synth.synth_light_sgs(3, L))
+    lobe, lam = torch.nn.functional.normalize(lgt[:, :3], dim=-1), lgt[:, 3:4].abs()
+    u = torch.from_numpy(g.random((2, L, nsamp), dtype=np.float32))
+    draws = {"dvis_theta": u[0][None].to(dev), "dvis_phi": u[1][None].to(dev)}
+    sd32 = on.as_torch(sd_np)
+    sd64 = _f64(sd32)
+    layers64 = [(sd64[on.VIS + "%d.weight" % (2 * i)], sd64[on.VIS + "%d.bias" % (2 * i)]) for i in range(5)]
+    seen = []
+
+    def vis64(p, d):              # the float64 oracle, noting the hidden activations of the pairs the kernels evaluate (the front-facing ones)
+        seen.append(_hidden_magnitudes(layers64, torch.cat([pe(p.double(), 10), pe(d.double(), 10)], -1), torch.relu, stride=16))
+        return on.vis_logits(sd64, p.double(), d.double())
+
+    # identical fp32 inputs for every column: the sampled directions and lobe weights the kernels themselves are handed (ops.dvis_dirs, on the
+    # device), the cull on them in fp32; the MLP, the soft-max and the lobe-weighted mean in float64 (r64) / PyTorch-CPU float32 (o32)
+    lgt7 = torch.zeros(L, 7)
+    lgt7[:, :3], lgt7[:, 3:4] = lobe, lam
+    dirs, wdir, wsum = (t.cpu() for t in ops.dvis_dirs(lgt7.to(dev), draws["dvis_theta"], draws["dvis_phi"], 1.0, direct=True))
+    dd = dirs.reshape(L * nsamp, 3)
+    front = (nrm.unsqueeze(1) * dd.unsqueeze(0)).sum(-1) > 1e-6
+    pi_, di_ = front.nonzero(as_tuple=True)
+
+    def oracle(vis_fn, dt):
+        vis = torch.zeros(n, L * nsamp, dtype=dt)
+        vis[front] = torch.softmax(vis_fn(pts[pi_], dd[di_]), -1)[..., 1]
+        return ((vis.reshape(n, L, nsamp) * wdir.reshape(1, L, nsamp).to(dt)).sum(-1) / wsum.reshape(1, L).to(dt)).t()
+
+    r64, o32 = oracle(vis64, torch.float64), oracle(lambda p, d: on.vis_logits(sd32, p, d), torch.float32)
+    assert r64.dtype == torch.float64 and o32.dtype == torch.float32 and r64.shape == (L, n)
+    mx012, mx3 = max(max(s[0][:3]) for s in seen), max(s[0][3] for s in seen)
+    med = float(np.median([m for s in seen for m in s[1][:3]]))
+    largest = lambda k: max(mx012 * 2.0 ** k, mx3 * 2.0 ** _head_split(k)[0])      # noqa: E731
+    ks = _regime_ks(mx012, med)
+    assert 32752.0 <= largest(ks["hot"]) < 65504.0 <= mx012 * 2.0 ** (ks["hot"] + 1), (mx012, mx3, ks)
+    assert ks["hot"] > 0 > ks["bf8_edge"] > ks["cold"] > ks["below"], (mx012, med, ks)
+    forms = {"f16x6-pt": "bf8", "f16x6-stream": "bf8"}
+    try:
+        _lib.legacy()
+        forms["f16x6-1t"] = "six"
+    except Exception:
+        pass
+    # rule | the 1e-4 / 4e-4 bar (the first regime below a form's window) | recorded only: at a median of 2^-26.5 the bf8 copy of an
+    # activation's third piece is off by up to BF8_BELOW_WINDOW_ABS_ERR = 2^-38 (tests/split_model.py), 2^-11.5 = 3.4e-4 of the operand: the
+    # operand model itself puts this regime beyond the bar, so nothing is asserted on its error but that it repeats bit for bit
+    window = {"six": ("base", "hot", "bf8_edge", "cold"), "bf8": ("base", "hot", "bf8_edge")}
+    barred = {"six": ("below",), "bf8": ("cold",)}
+
+    def run(k, mode):
+        sd = _pow2_regime(sd_np, on.VIS, k, *_head_split(k))
+        v = nets.VisNetwork(10, 10, [256] * 4)
+        v.load_state_dict({key[len("visibility_network."):]: torch.from_numpy(w) for key, w in sd.items()})
+        v = v.to(dev).eval()
+        monkeypatch.setattr(sg_render, "VIS_PRECISION", mode)
+        return sg_render.get_diffuse_visibility(pts.to(dev), nrm.to(dev), v, lobe.to(dev), lam.to(dev), nsamp=nsamp, draws=draws).cpu()
+
+    ops.range_check(sync=True)
+    k32_base, bad = None, []
+    st0 = {"o32": _quantiles(o32, r64)}
+    for regime, k in ks.items():
+        k32 = run(k, "fp32")
+        if regime == "base":
+            k32_base = k32
+        assert torch.equal(k32, k32_base), (regime, k, "fp32 itself left its range: the regime measures nothing")
+        st = dict(st0, k32=_quantiles(k32, r64))
+        for mode, kind in forms.items():
+            a = run(k, mode)
+            ops.range_check(sync=True)
+            st[mode] = _quantiles(a, r64)
+            if regime in window[kind]:
+                bad += [(regime,) + b for b in _rule_violations(st, mode)]
+            else:
+                assert torch.equal(a, run(k, mode)), (regime, mode)
+                assert bool(torch.isfinite(a).all()), (regime, mode)
+                if regime in barred[kind] and not (st[mode]["p99"] <= 1e-4 and st[mode]["max"] <= 4e-4):
+                    bad.append((regime, mode, "bar", st[mode]))
+        record_metric(f"pow2_regimes/light_visibility/{regime}", k=k, largest_hidden=largest(k), median_hidden_0_2=med * 2.0 ** k,
+                      entries=int(r64.numel()), **_flat(st))
+        print(f"light visibility {regime:9s} k {k:4d}  " + "  ".join(f"{c}: p50 {d['p50']:.2e} p99 {d['p99']:.2e} max {d['max']:.2e}" for c, d in st.items()))
+    for mode in forms:
+        run(ks["hot"] + 1, mode)
+        with pytest.raises(_lib.RobirHipError, match="overflowed its activation range") as ei:
+            ops.range_check(sync=True)
+        assert "light-visibility" in str(ei.value) and "rb_dvis_fused" in str(ei.value), (mode, str(ei.value))
+        ops.range_check(sync=True)
+    assert not bad, bad
