@@ -247,7 +247,9 @@ int rb_dvis_pblock_f16(const float* normals, const int* chunk_id, long n, const 
  *   tables of rb_octree_cast_*; the surviving (point, direction) pairs of each chunk, in the reference's order, are traced in
  *   lock-step batches of `batch_pairs` (reference: 2 000 000, sg_render.py:158) with max_iter (32) -- per batch the step size
  *   (0.01 beyond 100 000 rays, else 0.005) and the per-iteration fine-march count follow utils/octree.py:542-549.
- *   chunk_id must be ascending (points of a chunk contiguous).  No host synchronisation.  Scratch (device, caller-provided):
+ *   chunk_id must be ascending (points of a chunk contiguous).  batch_pairs >= L*nsamp (all pairs of a point fit one batch: a
+ *   point then spans at most two lock-step groups, which the per-group counters rest on); a smaller batch is refused, nothing is
+ *   launched.  No host synchronisation.  Scratch (device, caller-provided):
  *   pcount[n] i32, prank[n] i32, chunk_tab[4*n_chunks+4] i64, group_tab[2*max_groups] i64, counters[34*max_groups] i32,
  *   pair_p[cap] i32, pair_j[cap] u16, t_st[cap] f32, leaf_st[cap] i32, act_st[cap] u8, grp[cap] i32 (cap = n*L*nsamp),
  *   point_span[2n] i64, layout[4 + 8192] i64 (out: [0] pairs traced; [4 + 2 b], [5 + 2 b] = 32-byte octree records read / ray-iterations counted by workgroup b mod 4096 -- per-workgroup slots instead of device-wide atomics, the caller adds them up).  max_groups >= sum over chunks of

@@ -212,8 +212,9 @@ __global__ __launch_bounds__(256) void k_ovis_fill(Oct T, const float* __restric
   const float ox = points[3 * p], oy = points[3 * p + 1], oz = points[3 * p + 2];
   if (tid == 0) s_base = 0;
   __syncthreads();
-  // a point's pairs are consecutive in its chunk's order: they fall into at most two consecutive lock-step groups; the active
-  // counts go to the groups' counters once per point (one device-wide atomic per step and wave serialised on the counter)
+  // a point's pairs are consecutive in its chunk's order and at most L*nsamp <= batch (rb_dvis_octree refuses a smaller batch):
+  // they fall into at most two consecutive lock-step groups, gfirst and gfirst + 1; the active counts go to those two groups'
+  // counters once per point (one device-wide atomic per step and wave serialised on the counter)
   int gfirst = goff[c] + (int)((long)prank[p] / batch);
   if (gfirst >= max_groups) gfirst = max_groups - 1;
   int a0 = 0, a1 = 0;
@@ -568,10 +569,14 @@ static int dvis_octree_plain(const float* node, const float* nrm, long B, const 
   RB_REQUIRE(n_chunks >= 1 && (chunk_id || n_chunks == 1), "chunk_id is required for more than one chunk");
   RB_REQUIRE(max_iter > 0 && max_iter + 2 <= OV_ITERS, "secondary cast: 0 < max_iter <= 32");
   RB_REQUIRE(batch_pairs > 0 && max_groups >= 1, "bad batch size / group capacity");
+  char batch_msg[160];          // k_ovis_fill credits a point's active rays to at most two consecutive groups
+  snprintf(batch_msg, sizeof batch_msg, "batch_pairs = %ld is below L*nsamp = %ld: a point's pairs would span more than two lock-step groups",
+           batch_pairs, (long)L * nsamp);
+  RB_REQUIRE(batch_pairs >= (long)L * nsamp, batch_msg);
   hipStream_t s = (hipStream_t)stream;
   const int LS = L * nsamp;
   Oct T = make_oct(node, nrm, B, root_min, root_size, res);
-  // chunk_tab: cstart[C+1] | ctotal[C] | coff[C] | goff[C] (as int, in a long slot each);  group_tab: gstart[G] | gsize[G]
+  // chunk_tab: cstart[C+1] | ctotal[C] | coff[C] | goff[C] (int32, packed);  group_tab: gstart[max_groups] | gsize[max_groups]
   long* cstart = chunk_tab;
   long* ctotal = chunk_tab + (n_chunks + 1);
   long* coff = ctotal + n_chunks;
@@ -629,6 +634,10 @@ int rb_dvis_octree(const float* node, const float* nrm, long B, const float* roo
   RB_REQUIRE(n_chunks >= 1 && (chunk_id || n_chunks == 1), "chunk_id is required for more than one chunk");
   RB_REQUIRE(max_iter > 0 && max_iter + 2 <= OV_ITERS, "secondary cast: 0 < max_iter <= 32");
   RB_REQUIRE(batch_pairs > 0 && max_groups >= 1, "bad batch size / group capacity");
+  char batch_msg[160];          // k_ovis_fill credits a point's active rays to at most two consecutive groups
+  snprintf(batch_msg, sizeof batch_msg, "batch_pairs = %ld is below L*nsamp = %ld: a point's pairs would span more than two lock-step groups",
+           batch_pairs, (long)L * nsamp);
+  RB_REQUIRE(batch_pairs >= (long)L * nsamp, batch_msg);
   RB_REQUIRE((long)n * L * nsamp < 2147483647L, "pair indices are 32-bit: call in groups of chunks");
   hipStream_t s = (hipStream_t)stream;
   const int LS = L * nsamp;
