@@ -33,11 +33,15 @@ TRAIN_ABI_VERSION = 1
 VISTRAIN_PATH = os.path.join(_HERE, "librobir_hip_vistrain.so")
 _vistrain = None
 VISTRAIN_ABI_VERSION = 1
+ILLUMTRAIN_PATH = os.path.join(_HERE, "librobir_hip_illumtrain.so")
+_illumtrain = None
+ILLUMTRAIN_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
     """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library), librobir_hip_train.so (the
-    training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/) and -- legacy=True --
+    training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/),
+    librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/) and -- legacy=True --
     librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -141,6 +145,22 @@ def vistrain():
 def call_vistrain(name, *args):
     """An entry point of the visibility-training library."""
     _call_aux(vistrain(), name, *args)
+
+
+def illumtrain():
+    """The illumination-training library (include/robir_hip_illumtrain.h; `make -C robir_amd/csrc illumtrain`): the reverse mode of
+    IndirctIllumNetwork's lobe net, the fused SG query and its reverse."""
+    global _illumtrain
+    if _illumtrain is None:
+        _illumtrain = _load_aux(ILLUMTRAIN_PATH, ILLUMTRAIN_ABI_VERSION, "rb_it_", ("rb_it_lobe_bwd_scratch_bytes",), "illumtrain",
+                                "ILLUMINATION-TRAINING library librobir_hip_illumtrain.so",
+                                "indirect-illumination gradients and the SG query, robir_amd/illum_autograd.py")
+    return _illumtrain
+
+
+def call_illumtrain(name, *args):
+    """An entry point of the illumination-training library."""
+    _call_aux(illumtrain(), name, *args)
 
 
 def legacy_loaded():

@@ -1,5 +1,5 @@
-// The fp64 GEMM engine of the training libraries (librobir_hip_train.so: train/ae_bwd.hip, librobir_hip_vistrain.so: vistrain/vis_bwd.hip;
-// DESIGN 4.3, 4.5).  A reverse mode is three product families -- activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ -- and all of them
+// The fp64 GEMM engine of the training libraries (librobir_hip_train.so: train/ae_bwd.hip, librobir_hip_vistrain.so: vistrain/vis_bwd.hip,
+// librobir_hip_illumtrain.so: illumtrain/illum_bwd.hip).  A reverse mode is three product families -- activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ -- and all of them
 // run on v_mfma_f64_16x16x4_f64 through ONE tiled kernel, k_gemm64, whose operands are addressed by (row stride, column stride).  Included
 // once per library: everything here is internal to the including translation unit (each library keeps its own
 // last-error string and launch counter), and each library instantiates k_gemm64 for the one (activation family, reduction mode) it runs.
@@ -28,7 +28,9 @@ constexpr int LDS_LD = 80;                    // doubles per k-row of a tile in 
 constexpr double SLOPE = 0.2;                 // nn.LeakyReLU(0.2)
 
 enum { EPI_FWD = 0, EPI_BWD = 1, EPI_WGRAD = 2 };      // Gemm::epi (run-time)
-enum { ACT_LEAKY = 0, ACT_RELU = 1 };                  // compile-time: the activation of the hidden layers
+// compile-time: the activation of the hidden layers.  ACT_RELU_OPT: ReLU where Gemm::act is set, identity where it is not (a net whose
+// last forward launch keeps its pre-activation: the lobe net's raw output)
+enum { ACT_LEAKY = 0, ACT_RELU = 1, ACT_RELU_OPT = 2 };
 // compile-time: how a weight gradient (EPI_WGRAD) leaves the kernel.  RED_ACC: its reduction dimension is not split, one thread owns one
 // element of the fp64 accumulator and stores (first) or adds to it.  RED_PART: the reduction dimension is cut into partitions of part_rows,
 // blockIdx.z + part0 = partition q stores its own partial at C + q part_stride with plain vector stores (the library adds them in order).
@@ -43,8 +45,8 @@ struct Gemm {
     int epi;
     double* C; long ldc;
     const float* bias;        // EPI_FWD: + bias[n]
-    int act;                  // ACT_LEAKY only, per layer: EPI_FWD: the activation on the result.  EPI_BWD: result . act'(mask[m,n]), mask =
-                              // the stored activation.  An ACT_RELU library has no layer without it and applies it to every launch
+    int act;                  // ACT_LEAKY / ACT_RELU_OPT, per layer: EPI_FWD: the activation on the result.  EPI_BWD: result . act'(mask[m,n]),
+                              // mask = the stored activation.  An ACT_RELU library has no layer without it and applies it to every launch
     const double* mask; long ldm;
     int first;                // EPI_WGRAD, RED_ACC: 1 = store, 0 = add to what C holds (slab order)
     int part_rows, part0;     // EPI_WGRAD, RED_PART: k in [q part_rows, min((q + 1) part_rows, K))
@@ -119,10 +121,12 @@ __global__ __launch_bounds__(256) void k_gemm64(Gemm g) {
             if (g.epi == EPI_FWD) {
                 v += (double)g.bias[n];
                 if constexpr (ACT == ACT_RELU) v = v > 0.0 ? v : 0.0;
+                else if constexpr (ACT == ACT_RELU_OPT) v = !g.act || v > 0.0 ? v : 0.0;
                 else if (g.act) v = v > 0.0 ? v : SLOPE * v;
             } else if (g.epi == EPI_BWD) {
                 if constexpr (ACT == ACT_RELU) v = g.mask[(long)m * g.ldm + n] > 0.0 ? v : 0.0;
-                else if (g.act) v *= g.mask[(long)m * g.ldm + n] > 0.0 ? 1.0 : SLOPE;
+                else if constexpr (ACT == ACT_RELU_OPT) v = !g.act || g.mask[(long)m * g.ldm + n] > 0.0 ? v : 0.0;
+                else if (g.act) v *=g.mask[(long)m * g.ldm + n] > 0.0 ? 1.0 : SLOPE;
             } else if constexpr (RED == RED_ACC) {
                 if (!g.first) v = *c + v;
             }

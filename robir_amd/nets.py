@@ -11,8 +11,9 @@ a parameter that requires grad, raises ForwardOnlyError (`forward_only_guard`; t
 --plot_only rendering) instead of handing detached outputs to a loss.  Material NETWORKS therefore still train on
 the reference's modules; what IS differentiable on the HIP path is the SG shading of their outputs (robir_amd/sg_autograd.py,
 sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis) and -- after the explicit
-opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py), and -- after
-robir_amd.training.enable_visibility_training -- the visibility network (robir_amd/vis_autograd.py).
+opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py), -- after
+robir_amd.training.enable_visibility_training -- the visibility network (robir_amd/vis_autograd.py), and -- after
+robir_amd.training.enable_illumination_training -- the indirect-illumination network (robir_amd/illum_autograd.py).
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """
@@ -71,9 +72,10 @@ PRECISE_GRAD_SPLIT = os.environ.get("ROBIR_PRECISE_GRAD", "split") == "split"   
 def forward_only_guard(module):
     """The HIP kernels have no backward: a training-mode call that autograd would have to differentiate must not silently
     return detached tensors (loss.backward() would then train only whatever still carries a graph).  A module marked by
-    robir_amd.training.enable_material_training (or, a VisNetwork, by enable_visibility_training) has a backward and passes; its unmarked
-    sub-networks still raise."""
-    if getattr(module, "_material_training", False) or getattr(module, "_visibility_training", False):
+    robir_amd.training.enable_material_training (or, a VisNetwork, by enable_visibility_training; an IndirctIllumNetwork, by
+    enable_illumination_training) has a backward and passes; its unmarked sub-networks still raise."""
+    if (getattr(module, "_material_training", False) or getattr(module, "_visibility_training", False)
+            or getattr(module, "_illumination_training", False)):
         return
     if module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise ForwardOnlyError(f"{type(module).__name__}: robir_amd kernels are forward-only -- call .eval(), wrap the call in "
@@ -338,29 +340,41 @@ class IndirctIllumNetwork(nn.Module):
     _BLOBS = {"lobe": ("pack_illum", "indirect_illum_network.lobe_layer.", {}), "lobe_h3": ("pack_illum_h3", "indirect_illum_network.lobe_layer.", {}),
               "lobe_x6": ("pack_illum_x6", "indirect_illum_network.lobe_layer.", {})}
 
+    def _trainable(self):
+        """Marked by robir_amd.training.enable_illumination_training, grad mode on, a parameter that requires grad: calls build a graph."""
+        return (getattr(self, "_illumination_training", False) and torch.is_grad_enabled()
+                and any(p.requires_grad for p in self.parameters()))
+
+    def _lobes(self, points, hdr, X=None):
+        """lgt_sgs [n,24,7] of points [n,3] and hdr [n,1] (None: no_hdr) under the current precision policy; X: their feature rows, if at hand."""
+        r = dispatch.wide(mlp_precision(), ops.SDF_FUSED_PE, points=True, encoder=False)
+        blob = self._packed.blob(r.blob, self.lobe_layer, self._BLOBS)
+        if r.encode:        # feature rows; else [PE10(x) | hdr_shift] encoded inside the lobe net's kernel
+            if X is None:
+                X = ops.feat_pe10(points, extra=hdr)
+            return ops.illum_decode(getattr(ops, r.fn)(X, blob, *((False,) if r.flag else ()), **_h3(r)))
+        return ops.illum_decode(getattr(ops, r.fn)(points, hdr, blob, False, **_h3(r)))
+
+    def _integral(self, X, noise):
+        """env_int [n,3]: only the perturbed pass is used (implicit_differentiable_renderer.py:220)."""
+        return ops.abs_scale(self.integral_layer.run_pass(ops.axpy(X, noise, 0.02)), 1.0)
+
     def forward(self, points, hdr_shift, noise=None):
         forward_only_guard(self)
         n = points.shape[0]
         dev = points.device
-        X = ops.feat_pe10(points.float().contiguous(), extra=hdr_shift.float().contiguous() if self.use_hdr else None)
         if noise is None:
             noise = torch.randn(n, 64, device=dev)
         elif noise.shape[1] < 64:                # no_hdr: the reference draws randn_like of the 63 embedded columns
             noise = torch.nn.functional.pad(noise, (0, 64 - noise.shape[1]))
+        if self._trainable():
+            from . import illum_autograd
+            return illum_autograd.forward(self, points, hdr_shift, noise)
+        points = points.float().contiguous()
+        hdr = hdr_shift.float().contiguous() if self.use_hdr else None
+        X = ops.feat_pe10(points, extra=hdr)
         noise = noise.float().contiguous()
-
-        def lobes():
-            r = dispatch.wide(mlp_precision(), ops.SDF_FUSED_PE, points=True, encoder=False)
-            blob = self._packed.blob(r.blob, self.lobe_layer, self._BLOBS)
-            if r.encode:        # feature rows; else [PE10(x) | hdr_shift] encoded inside the lobe net's kernel
-                return ops.illum_decode(getattr(ops, r.fn)(X, blob, *((False,) if r.flag else ()), **_h3(r)))
-            hdr = hdr_shift.float().contiguous() if self.use_hdr else None
-            return ops.illum_decode(getattr(ops, r.fn)(points, hdr, blob, False, **_h3(r)))
-
-        def integral():       # only the perturbed pass is used (implicit_differentiable_renderer.py:220)
-            return ops.abs_scale(self.integral_layer.run_pass(ops.axpy(X, noise, 0.02)), 1.0)
-
-        sgs, integ = run_concurrently([lobes, integral], n)      # two independent nets
+        sgs, integ = run_concurrently([lambda: self._lobes(points, hdr, X), lambda: self._integral(X, noise)], n)      # two independent nets
         return sgs, integ
 
 

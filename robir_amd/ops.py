@@ -539,6 +539,63 @@ def vis_backward(points, dirs, rep, params, g_logits, want=VIS_PARAM_NAMES, slab
     return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
 
 
+ILLUM_PARAM_NAMES = tuple(f"lobe_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias"))
+# A step of the "Illum" stage is n_hit rows (not n_hit x nsamp): at the 650 hit points of a 1024-pixel chunk, 256-row partitions make the
+# widest weight gradient (512 x 513: 72 output tiles) 72 x 3 = 216 workgroups on 256 compute units.  The default rests on that workgroup
+# count, not on a measured time.  Scratch: 148 MB for a full slab, 31 MB at 650 rows
+ILLUM_SLAB_ROWS = 4096
+ILLUM_PART_ROWS = 256
+
+
+def illum_lobe_backward(points, hdr, params, g_sgs, want=ILLUM_PARAM_NAMES, slab_rows=None, part_rows=None):
+    """Reverse mode of IndirctIllumNetwork's lobe net (rb_it_lobe_bwd, include/robir_hip_illumtrain.h): points [n,3], hdr [n,1] or None (the
+    no_hdr net, whose first weight is [512,63]), params = the ten nn.Linear tensors in ILLUM_PARAM_NAMES order, g_sgs [n,24,7] the upstream
+    gradient on the decoded lobes.  -> (dict name -> gradient in the parameter's own shape for the names in `want`, stats dict: kernels
+    enqueued, lowest layer differentiated, partitions per full slab, scratch bytes).  Allocates the wanted gradients and the scratch,
+    nothing else."""
+    points = _f32(points.detach())
+    n, dev = points.shape[0], points.device
+    hdr = None if hdr is None else _f32(hdr.detach()).reshape(n, 1)
+    assert points.dim() == 2 and points.shape[1] == 3 and len(params) == 10
+    params = [_f32(p.detach()) for p in params]
+    assert tuple(params[0].shape) == (512, 63 if hdr is None else 64), "lobe_layer.0.weight is [512,64] with hdr, [512,63] without"
+    g_sgs = _f32(g_sgs.detach()).reshape(n, 24, 7)
+    slab = int(slab_rows or ILLUM_SLAB_ROWS)
+    part = int(part_rows or min(slab, ILLUM_PART_ROWS))
+    stats = (c_int * 3)(0, 5, 0)
+    out, nbytes = _param_backward(
+        "illum_lobe_backward", ILLUM_PARAM_NAMES, params, want, rows=n, dev=dev, lib=_lib.illumtrain, query="rb_it_lobe_bwd_scratch_bytes",
+        query_args=(c_long(n), c_long(slab), c_long(part)),
+        launch=lambda P, G, scratch, nbytes: _lib.call_illumtrain(
+            "rb_it_lobe_bwd", ptr(points), ptr(hdr), c_long(n), P, ptr(g_sgs), G, c_long(slab), c_long(part), ptr(scratch), c_long(nbytes),
+            stats, stream_ptr()))
+    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+
+
+def _sg_query_args(sgs, dirs):
+    sgs, dirs = _f32(sgs.detach()), _f32(dirs.detach())
+    assert sgs.dim() == 3 and sgs.shape[2] == 7 and dirs.dim() == 3 and dirs.shape[2] == 3 and dirs.shape[0] == sgs.shape[0]
+    return sgs, dirs, sgs.shape[0], sgs.shape[1], dirs.shape[1]
+
+
+def sg_query(sgs, dirs):
+    """query_indir_illum (model/loss.py:128-141), fused (rb_it_sg_query): sgs [n,L,7], dirs [n,S,3] -> radiance [n,S,3] =
+    sum_j mu_j exp(lambda_j (d . l_j / |l_j| - 1)), fp64 from the fp32 inputs, rounded once."""
+    sgs, dirs, n, L, S = _sg_query_args(sgs, dirs)
+    rad = torch.empty(n, S, 3, dtype=torch.float32, device=sgs.device)
+    _lib.call_illumtrain("rb_it_sg_query", ptr(sgs), ptr(dirs), c_long(n), c_int(L), c_long(S), ptr(rad), stream_ptr())
+    return rad
+
+
+def sg_query_backward(sgs, dirs, g):
+    """d <g, sg_query(sgs, dirs)> / d sgs (rb_it_sg_query_bwd): g [n,S,3] dense, zeros at masked samples -> [n,L,7]."""
+    sgs, dirs, n, L, S = _sg_query_args(sgs, dirs)
+    g = _f32(g.detach()).reshape(n, S, 3)
+    out = torch.empty(n, L, 7, dtype=torch.float32, device=sgs.device)
+    _lib.call_illumtrain("rb_it_sg_query_bwd", ptr(sgs), ptr(dirs), ptr(g), c_long(n), c_int(L), c_long(S), ptr(out), stream_ptr())
+    return out
+
+
 def axpy(a, b, s):
     a, b = _f32(a), _f32(b)
     y = torch.empty_like(a)

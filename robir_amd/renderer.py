@@ -170,7 +170,8 @@ class IDRNetwork(nn.Module):
         chunk = N if not chunk or N <= chunk else int(chunk)
         limit = self.__dict__.get("deferred_chunks", deferred.DEFAULT_CHUNKS)
         if (limit and not self.training and chunk == N and N <= 1024 and self.use_octree and draws is None and stats is None
-                and input.get("albedo_ratio") is None and self._tex_uv is None and not fun_spec):
+                and input.get("albedo_ratio") is None and self._tex_uv is None and not fun_spec
+                and not self.indirect_illum_network._trainable()):       # a forward that builds a graph runs at once
             rec = self._record_chunk(input, N, int(limit), trainstage, fun_spec, lin_diff)
             if rec is not None:
                 return rec

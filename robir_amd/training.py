@@ -15,7 +15,12 @@ kl_sparsity / latent_smooth restate the two stage-3 regularisers of model/loss.p
 The same opt-in exists for the "Vis" stage (training/train_visibility.py:297-308: the optimiser holds visibility_network):
 enable_visibility_training marks a VisNetwork.  With the mark, grad mode on and a parameter that requires grad, VisNetwork.forward /
 logits_from_points return logits with a graph to the ten nn.Linear tensors (robir_amd/vis_autograd.py -> librobir_hip_vistrain.so), and
-IDRNetwork.trace_radiance's pred_vis carries that graph; visibility_loss restates the stage's cross-entropy (model/loss.py:173-177)."""
+IDRNetwork.trace_radiance's pred_vis carries that graph; visibility_loss restates the stage's cross-entropy (model/loss.py:173-177).
+
+The stage's other optimiser step (training/train_visibility.py:309-313) trains indirect_illum_network: enable_illumination_training marks an
+IndirctIllumNetwork.  With the mark, grad mode on and a parameter that requires grad, IndirctIllumNetwork.forward returns (lgt_sgs, env_int)
+with a graph to lobe_layer and integral_layer (robir_amd/illum_autograd.py -> librobir_hip_illumtrain.so, librobir_hip_train.so), the model's
+indirect_sgs / indir_integral carry it, and radiance_loss restates model/loss.py:156-171 on the fused, differentiable query_indir_illum."""
 import torch
 
 from . import nets
@@ -105,3 +110,54 @@ def visibility_loss(pred_vis, gt_vis, points_mask):
     pred = pred_vis[mask].reshape(-1, 2)
     gt = (~gt_vis[mask].bool()).long().reshape(-1)
     return torch.nn.functional.cross_entropy(pred, gt)
+
+
+def _illumination_network(obj):
+    if isinstance(obj, nets.IndirctIllumNetwork):
+        return obj
+    net = getattr(obj, "indirect_illum_network", None)
+    if isinstance(net, nets.IndirctIllumNetwork):
+        return net
+    return None
+
+
+def enable_illumination_training(net, on=True):
+    """Mark (on=False: unmark) an IndirctIllumNetwork -- or the one a model holds as .indirect_illum_network -- as trainable on the HIP path.
+    Returns the illumination network.  Its integral_layer stays unmarked: the network's forward differentiates it as one clean pass on the
+    perturbed rows, the stand-alone SparseAE(smooth_on_latent=False) forward keeps its refusal."""
+    ill = _illumination_network(net)
+    if ill is None:
+        raise TypeError(f"enable_illumination_training: {type(net).__name__} is neither an IndirctIllumNetwork nor a model that has one")
+    ill._illumination_training = bool(on)
+    return ill
+
+
+def illumination_training_enabled(net):
+    return bool(getattr(_illumination_network(net), "_illumination_training", False))
+
+
+def query_indir_illum(lgtSGs, sample_dirs):
+    """model/loss.py:128-141 under the reference's name and argument order, fused and differentiable in the lobes: lgtSGs [n,L,7],
+    sample_dirs [n,S,3] -> radiance [n,S,3] = sum_j mu_j exp(lambda_j (d . l_j / |l_j| - 1)).  sample_dirs is a constant."""
+    from . import illum_autograd
+    return illum_autograd.sg_query(lgtSGs, sample_dirs)
+
+
+def radiance_loss(model_outputs, trace_outputs, anneal_t=0.0, loss_type="L1", query=None):
+    """The radiance term of IllumLoss.forward (model/loss.py:156-171): with points_mask = network_object_mask [N] and indir_mask [N,S], the
+    mean L1 (loss_type "L2": mean squared) distance between trace_radiance[indir_mask] + anneal_t and
+    query(indirect_sgs[points_mask], sample_dirs)[indir_mask[points_mask]], plus the same distance between gt_integral[points_mask] and
+    indir_integral[points_mask].  query: query_indir_illum's signature; the fused one by default."""
+    if loss_type == "L1":
+        dist = torch.nn.functional.l1_loss
+    elif loss_type == "L2":
+        dist = torch.nn.functional.mse_loss
+    else:
+        raise ValueError(f"radiance_loss: unknown loss_type {loss_type!r} (L1 | L2)")
+    query = query or query_indir_illum
+    indir_mask = trace_outputs["indir_mask"].bool()
+    points_mask = model_outputs["network_object_mask"].reshape(-1).bool()
+    gt_radiance = trace_outputs["trace_radiance"][indir_mask] + anneal_t
+    pred_radiance = query(model_outputs["indirect_sgs"][points_mask], trace_outputs["sample_dirs"])
+    loss = dist(pred_radiance[indir_mask[points_mask]], gt_radiance)
+    return loss + dist(model_outputs["indir_integral"][points_mask], trace_outputs["gt_integral"][points_mask])
