@@ -36,12 +36,16 @@ VISTRAIN_ABI_VERSION = 1
 ILLUMTRAIN_PATH = os.path.join(_HERE, "librobir_hip_illumtrain.so")
 _illumtrain = None
 ILLUMTRAIN_ABI_VERSION = 1
+CESRTRAIN_PATH = os.path.join(_HERE, "librobir_hip_cesrtrain.so")
+_cesrtrain = None
+CESRTRAIN_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
     """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library), librobir_hip_train.so (the
     training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/),
-    librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/) and -- legacy=True --
+    librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/),
+    librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/) and -- legacy=True --
     librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -161,6 +165,21 @@ def illumtrain():
 def call_illumtrain(name, *args):
     """An entry point of the illumination-training library."""
     _call_aux(illumtrain(), name, *args)
+
+
+def cesrtrain():
+    """The CESR-training library (include/robir_hip_cesrtrain.h; `make -C robir_amd/csrc cesrtrain`): the reverse mode of the CESR stage's
+    shadow_net and normal_net."""
+    global _cesrtrain
+    if _cesrtrain is None:
+        _cesrtrain = _load_aux(CESRTRAIN_PATH, CESRTRAIN_ABI_VERSION, "rb_ct_", ("rb_ct_cesr_bwd_scratch_bytes",), "cesrtrain",
+                               "CESR-TRAINING library librobir_hip_cesrtrain.so", "shadow_net / normal_net gradients, robir_amd/cesr_autograd.py")
+    return _cesrtrain
+
+
+def call_cesrtrain(name, *args):
+    """An entry point of the CESR-training library."""
+    _call_aux(cesrtrain(), name, *args)
 
 
 def legacy_loaded():

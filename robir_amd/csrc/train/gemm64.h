@@ -1,5 +1,5 @@
 // The fp64 GEMM engine of the training libraries (librobir_hip_train.so: train/ae_bwd.hip, librobir_hip_vistrain.so: vistrain/vis_bwd.hip,
-// librobir_hip_illumtrain.so: illumtrain/illum_bwd.hip).  A reverse mode is three product families -- activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ -- and all of them
+// librobir_hip_illumtrain.so: illumtrain/illum_bwd.hip, librobir_hip_cesrtrain.so: cesrtrain/cesr_bwd.hip).  A reverse mode is three product families -- activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ -- and all of them
 // run on v_mfma_f64_16x16x4_f64 through ONE tiled kernel, k_gemm64, whose operands are addressed by (row stride, column stride).  Included
 // once per library: everything here is internal to the including translation unit (each library keeps its own
 // last-error string and launch counter), and each library instantiates k_gemm64 for the one (activation family, reduction mode) it runs.
@@ -29,8 +29,10 @@ constexpr double SLOPE = 0.2;                 // nn.LeakyReLU(0.2)
 
 enum { EPI_FWD = 0, EPI_BWD = 1, EPI_WGRAD = 2 };      // Gemm::epi (run-time)
 // compile-time: the activation of the hidden layers.  ACT_RELU_OPT: ReLU where Gemm::act is set, identity where it is not (a net whose
-// last forward launch keeps its pre-activation: the lobe net's raw output)
-enum { ACT_LEAKY = 0, ACT_RELU = 1, ACT_RELU_OPT = 2 };
+// last forward launch keeps its pre-activation: the lobe net's raw output).  ACT_SOFTPLUS100_OPT: softplus(beta = 100) where Gemm::act is
+// set: the stored activation is a = z above torch's threshold (100 z > 20), log1p(exp(100 z)) / 100 below, and the gate is recovered from
+// it as sigmoid(100 z) = -expm1(-100 a) (above the threshold that is 1 - exp(-100 z), within 2e-9 of torch's exact 1: no special case)
+enum { ACT_LEAKY = 0, ACT_RELU = 1, ACT_RELU_OPT = 2, ACT_SOFTPLUS100_OPT = 3 };
 // compile-time: how a weight gradient (EPI_WGRAD) leaves the kernel.  RED_ACC: its reduction dimension is not split, one thread owns one
 // element of the fp64 accumulator and stores (first) or adds to it.  RED_PART: the reduction dimension is cut into partitions of part_rows,
 // blockIdx.z + part0 = partition q stores its own partial at C + q part_stride with plain vector stores (the library adds them in order).
@@ -122,10 +124,12 @@ __global__ __launch_bounds__(256) void k_gemm64(Gemm g) {
                 v += (double)g.bias[n];
                 if constexpr (ACT == ACT_RELU) v = v > 0.0 ? v : 0.0;
                 else if constexpr (ACT == ACT_RELU_OPT) v = !g.act || v > 0.0 ? v : 0.0;
+                else if constexpr (ACT == ACT_SOFTPLUS100_OPT) v = !g.act || 100.0 * v > 20.0 ? v : log1p(exp(100.0 * v)) / 100.0;
                 else if (g.act) v = v > 0.0 ? v : SLOPE * v;
             } else if (g.epi == EPI_BWD) {
                 if constexpr (ACT == ACT_RELU) v = g.mask[(long)m * g.ldm + n] > 0.0 ? v : 0.0;
                 else if constexpr (ACT == ACT_RELU_OPT) v = !g.act || g.mask[(long)m * g.ldm + n] > 0.0 ? v : 0.0;
+                else if constexpr (ACT == ACT_SOFTPLUS100_OPT) v = g.act ? v * -expm1(-100.0 * g.mask[(long)m * g.ldm + n]) : v;
                 else if (g.act) v *=g.mask[(long)m * g.ldm + n] > 0.0 ? 1.0 : SLOPE;
             } else if constexpr (RED == RED_ACC) {
                 if (!g.first) v = *c + v;

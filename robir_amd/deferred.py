@@ -236,6 +236,14 @@ def lazy_like(x, fn):
     return DeferredTensor(meta, x._rb_dev, lambda: fn(materialize(x)))
 
 
+def hook_trains(hook):
+    """A shading hook that holds a trainable CESR network (renderer.CESRHook with a net marked by training.enable_cesr_training, grad mode
+    on, a parameter that requires grad): its chunk forward builds a graph, so it is never recorded -- it runs at once and pending chunks
+    are flushed (a recorded pass runs under no_grad and would drop the graph)."""
+    nets = (getattr(hook, "shadow_net", None), getattr(hook, "normal_net", None))
+    return any(callable(getattr(n, "_trainable", None)) and n._trainable() for n in nets)
+
+
 def flush_all():
     """Run every recorded pass (called before anything that changes what a pass would compute)."""
     for q in list(_LIVE):

@@ -13,7 +13,8 @@ the reference's modules; what IS differentiable on the HIP path is the SG shadin
 sg_render.render_with_all_sg: light SGs, f0, roughness, albedo, metallic, indirect integral, predicted diffuse_vis) and -- after the explicit
 opt-in robir_amd.training.enable_material_training -- the spec auto-encoder of EnvmapMaterialNetwork (robir_amd/ae_autograd.py), -- after
 robir_amd.training.enable_visibility_training -- the visibility network (robir_amd/vis_autograd.py), and -- after
-robir_amd.training.enable_illumination_training -- the indirect-illumination network (robir_amd/illum_autograd.py).
+robir_amd.training.enable_illumination_training -- the indirect-illumination network (robir_amd/illum_autograd.py), and -- after
+robir_amd.training.enable_cesr_training -- the CESR stage's shadow_net / normal_net (robir_amd/cesr_autograd.py).
 Every forward that the reference randomises takes the draws as an optional explicit tensor (`noise=`); when omitted
 they are drawn with torch.randn on the device, in the reference's order.
 """
@@ -73,9 +74,10 @@ def forward_only_guard(module):
     """The HIP kernels have no backward: a training-mode call that autograd would have to differentiate must not silently
     return detached tensors (loss.backward() would then train only whatever still carries a graph).  A module marked by
     robir_amd.training.enable_material_training (or, a VisNetwork, by enable_visibility_training; an IndirctIllumNetwork, by
-    enable_illumination_training) has a backward and passes; its unmarked sub-networks still raise."""
+    enable_illumination_training; an SDFNetwork of kind shadow / normal, by enable_cesr_training) has a backward and passes; its unmarked
+    sub-networks still raise."""
     if (getattr(module, "_material_training", False) or getattr(module, "_visibility_training", False)
-            or getattr(module, "_illumination_training", False)):
+            or getattr(module, "_illumination_training", False) or getattr(module, "_cesr_training", False)):
         return
     if module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise ForwardOnlyError(f"{type(module).__name__}: robir_amd kernels are forward-only -- call .eval(), wrap the call in "
@@ -587,22 +589,52 @@ class SDFNetwork(nn.Module):
     def _cesr_route(self, r, x, M, kind, n_label):
         return getattr(ops, r.fn)(x, M, kind, self._blob(r.blob), n_label=n_label, **_h3(r))
 
-    def _cesr(self, X, M, kind, n_label=1):
+    def _trainable(self):
+        """Marked by robir_amd.training.enable_cesr_training, grad mode on, a parameter that requires grad: calls build a graph."""
+        return (getattr(self, "_cesr_training", False) and torch.is_grad_enabled()
+                and any(p.requires_grad for p in self.parameters()))
+
+    def _cesr_eval(self, x, M, kind, n_label, points):
+        """The forward-only route of the current policy: on points (encoding inside the kernel, whatever ROBIR_SDF_FUSED_PE says) or on rows."""
+        r = dispatch.cesr(mlp_precision(), cesr_precision(), True if points else ops.SDF_FUSED_PE, points=points)
+        return self._cesr_route(r, x, M, kind, n_label)
+
+    def _cesr_head(self, x, M, kind, n_label, points, head):
+        """head 0: the raw output; 1: ops.softmax2(., 1); 2: ops.normalize3(., 1e-4, 1).  Through robir_amd/cesr_autograd.py when trainable."""
         forward_only_guard(self)
-        return self._cesr_route(dispatch.cesr(mlp_precision(), cesr_precision(), ops.SDF_FUSED_PE, points=False), X, M, kind, n_label)
+        if self._trainable():
+            from . import cesr_autograd
+            return cesr_autograd.apply(self, x, M, kind, n_label, points, head)
+        from .cesr_autograd import HEADS
+        return HEADS[head](self._cesr_eval(x, M, kind, n_label, points))
+
+    def _cesr(self, X, M, kind, n_label=1):
+        return self._cesr_head(X, M, kind, n_label, False, 0)
 
     def _cesr_points(self, pts, M, kind, n_label=1):
         """_cesr on PE10(pts) with the encoding evaluated inside the kernel (kind 0 normal_net, 2 shadow_net x labels), whatever
         ROBIR_SDF_FUSED_PE says: a caller that honours it asks dispatch.cesr itself (renderer.CESRHook)."""
-        forward_only_guard(self)
-        return self._cesr_route(dispatch.cesr(mlp_precision(), cesr_precision(), True, points=True), pts, M, kind, n_label)
+        return self._cesr_head(pts, M, kind, n_label, True, 0)
 
     def eval_point_labels(self, Xp, n_label=128):
-        """shadow_net on every (point, one-hot label) pair: Xp [n,64] PE10 features -> logits [n*n_label, 2]."""
+        """shadow_net on every (point, one-hot label) pair: Xp [n,64] PE10 features, or the points [n,3] themselves (encoded inside the
+        kernel) -> logits [n*n_label, 2]."""
         assert self.kind == "shadow"
-        if Xp.shape[1] == 3:            # points [n,3]: encoded inside the kernel
-            return self._cesr_points(Xp, Xp.shape[0] * n_label, 2, n_label)
-        return self._cesr(Xp, Xp.shape[0] * n_label, 2, n_label)
+        return self._cesr_head(Xp, Xp.shape[0] * n_label, 2, n_label, Xp.shape[1] == 3, 0)
+
+    def diffuse_vis(self, Xp, n_label=128):
+        """shadow_net's predicted visibility of every (point, label) pair, ops.softmax2(eval_point_labels(Xp, n_label), 1) [n*n_label]: with
+        a graph to the network's parameters when it is trainable (cesr_autograd.VisFn); forward-only it IS that expression."""
+        assert self.kind == "shadow"
+        if self._trainable():
+            return self._cesr_head(Xp, Xp.shape[0] * n_label, 2, n_label, Xp.shape[1] == 3, 1)
+        return ops.softmax2(self.eval_point_labels(Xp, n_label), 1)
+
+    def unit_normal(self, Xp):
+        """normal_net's unit normal, ops.normalize3(raw, 1e-4, 1) [n,3], of PE10 features [n,64] or points [n,3]: with a graph to the
+        network's parameters when it is trainable (cesr_autograd.UnitFn)."""
+        assert self.kind == "normal"
+        return self._cesr_head(Xp, Xp.shape[0], 0, 1, Xp.shape[1] == 3, 2)
 
     def forward(self, inputs, var=0.0001, chunk=1024):
         if inputs.numel() == 0:

@@ -572,6 +572,43 @@ def illum_lobe_backward(points, hdr, params, g_sgs, want=ILLUM_PARAM_NAMES, slab
     return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
 
 
+CESR_PARAM_NAMES = tuple(f"lin{l}.{w}" for l in range(9) for w in ("weight_g", "weight_v", "bias"))
+CESR_KINDS = {"normal": (0, 63, 3), "shadow": (1, 191, 2)}       # SDFNetwork.kind -> (the library's kind code, d_in, d_out)
+# One 1024-pixel chunk sends ~940 points x 128 labels = 120 000 rows through shadow_net: seven full slabs and a short one at 16384 rows.
+# The fastest on an MI355X of (4096, 512) 95 ms, (16384, 1024) 68 ms, (16384, 2048) 76 ms: profiles/cesr_backward_times.md.  Scratch: 42.6 KB
+# per slab row, 727 MiB at these defaults
+CESR_SLAB_ROWS = 16384
+CESR_PART_ROWS = 1024
+
+
+def cesr_backward(x, M, kind, params, g_out, head=0, n_label=1, want=CESR_PARAM_NAMES, slab_rows=None, part_rows=None):
+    """Reverse mode of a CESR network (rb_ct_cesr_bwd, include/robir_hip_cesrtrain.h).  kind "normal" | "shadow"; x: points [M / n_label, 3]
+    (the points form: encoded in fp64 by the library, the one-hot label block built from the row index) or dense rows [M, ld >= d_in] (the
+    caller's fp32 rows); params = the 27 weight-norm tensors in CESR_PARAM_NAMES order; head 0: g_out [M, d_out] on the raw output, 1:
+    g_out [M] on softmax2(., 1) (shadow), 2: g_out [M, 3] on normalize3(., 1e-4, 1) (normal).  -> (dict name -> gradient in the parameter's
+    own shape for the names in `want`, stats dict: kernels enqueued, lowest layer differentiated, partitions per full slab, scratch bytes).
+    Allocates the wanted gradients and the scratch, nothing else."""
+    code, d_in, d_out = CESR_KINDS[kind]
+    x = _f32(x.detach())
+    M, dev = int(M), x.device
+    points = x.dim() == 2 and x.shape[1] == 3
+    assert x.dim() == 2 and len(params) == 27 and n_label >= 1 and M % n_label == 0
+    assert (x.shape[0] * n_label == M) if points else (x.shape[0] == M and x.shape[1] >= d_in), "points [M / n_label, 3] or rows [M, >= d_in]"
+    params = [_f32(p.detach()) for p in params]
+    assert tuple(params[1].shape) == (512, d_in) and tuple(params[25].shape) == (d_out, 512), f"not the {kind} network's tensors"
+    g_out = _f32(g_out.detach()).reshape((M,) if head == 1 else (M, d_out))
+    slab = int(slab_rows or CESR_SLAB_ROWS)
+    part = int(part_rows or min(slab, CESR_PART_ROWS))
+    stats = (c_int * 3)(0, 9, 0)
+    out, nbytes = _param_backward(
+        "cesr_backward", CESR_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.cesrtrain, query="rb_ct_cesr_bwd_scratch_bytes",
+        query_args=(c_long(M), c_long(slab), c_long(part)),
+        launch=lambda P, G, scratch, nbytes: _lib.call_cesrtrain(
+            "rb_ct_cesr_bwd", ptr(x if points else None), ptr(None if points else x), c_long(x.shape[1]), c_long(M), c_int(code),
+            c_int(n_label), c_int(head), P, ptr(g_out), G, c_long(slab), c_long(part), ptr(scratch), c_long(nbytes), stats, stream_ptr()))
+    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+
+
 def _sg_query_args(sgs, dirs):
     sgs, dirs = _f32(sgs.detach()), _f32(dirs.detach())
     assert sgs.dim() == 3 and sgs.shape[2] == 7 and dirs.dim() == 3 and dirs.shape[2] == 3 and dirs.shape[0] == sgs.shape[0]

@@ -171,7 +171,8 @@ class IDRNetwork(nn.Module):
         limit = self.__dict__.get("deferred_chunks", deferred.DEFAULT_CHUNKS)
         if (limit and not self.training and chunk == N and N <= 1024 and self.use_octree and draws is None and stats is None
                 and input.get("albedo_ratio") is None and self._tex_uv is None and not fun_spec
-                and not self.indirect_illum_network._trainable()):       # a forward that builds a graph runs at once
+                and not self.indirect_illum_network._trainable()       # a forward that builds a graph runs at once
+                and not deferred.hook_trains(self.get_sg_render)):
             rec = self._record_chunk(input, N, int(limit), trainstage, fun_spec, lin_diff)
             if rec is not None:
                 return rec
@@ -413,6 +414,12 @@ class IDRNetwork(nn.Module):
             bg = outs.pop()
         ret.update({"gradient_error": gerr, "bg_rgb": bg, "surface_mask": hit})
         ret.update(dict(zip(keys3 + keys1, outs)))
+        if r is not None and deferred.hook_trains(self.get_sg_render):
+            # a trainable CESR net behind CESRHook: its outputs with a graph go in again by ordinary torch, which carries it.  Every other
+            # forward keeps the scatter's graph-free outputs, as before
+            for k in keys3:
+                if isinstance(r[k], torch.Tensor) and r[k].requires_grad:
+                    ret[k] = ret[k].index_put((idx,), r[k].float())
         if fun_spec:
             for k in ("sg_specular_rgb", "indir_specular_rgb"):
                 def spec_values_fn(roughness, draws=None, buf=ret[k], fn=spec_fn.get(k)):
@@ -530,11 +537,13 @@ class CESRHook:
         rows = dispatch.cesr(mlp_precision(), cesr_precision(), ops.SDF_FUSED_PE, points=True).encode
         if rows:        # else shadow_net / normal_net straight from the points (encoding inside the kernels)
             x = ops.feat_pe10(x)
-        logits = self.shadow_net.eval_point_labels(x, 128)
-        normal_new = ops.normalize3((self.normal_net._cesr if rows else self.normal_net._cesr_points)(x, x.shape[0], 0), 1e-4, 1)
-        diffuse_vis = ops.softmax2(logits, 1)
+        # marked, trainable nets (training.enable_cesr_training): diffuse_vis carries its graph into the shading (rb_sg_shade_bwd hands its
+        # gradient back), normal_new into the consistency term below.  The shading takes normal_new DETACHED: it has no gradient with
+        # respect to the normal (a deliberate difference from the reference, whose image loss also reaches normal_net)
+        diffuse_vis = self.shadow_net.diffuse_vis(x, 128)
+        normal_new = self.normal_net.unit_normal(x)
         albedo = mat["sg_diffuse_albedo"]
-        ret = sg_render.render_with_all_sg(points=points, normal=normal_new if self.cur_iter > 1000 else mat["sg_normal_map"],
+        ret = sg_render.render_with_all_sg(points=points, normal=normal_new.detach() if self.cur_iter > 1000 else mat["sg_normal_map"],
                                            viewdirs=vd, lgtSGs=mat["sg_lgtSGs"], indir_integral=ops.abs_scale(indir_integral, 2 * np.pi, take_abs=False),
                                            specular_reflectance=mat["sg_specular_reflectance"].abs(),
                                            roughness=mat["sg_roughness"], diffuse_albedo=albedo,
@@ -542,8 +551,9 @@ class CESRHook:
                                            lin_diff=True, testing=not self.is_training, metallic=None,
                                            diffuse_vis=diffuse_vis, prefit=self.prefit, argmax_vis=self.argmax_vis,
                                            draws=draws, chunk_id=chunk_id, n_chunks=n_chunks, stats=stats)
-        ret["sg_rgb"] = ops.lin_diff_combine(ret["sg_diffuse_rgb"], albedo, ret["sg_specular_rgb"])
-        ret["indir_rgb"] = ops.lin_diff_combine(ret["indir_diffuse_rgb"], albedo, ret["indir_specular_rgb"])
+        from .cesr_autograd import lin_diff_combine          # ops.lin_diff_combine; with a graph where an input carries one
+        ret["sg_rgb"] = lin_diff_combine(ret["sg_diffuse_rgb"], albedo, ret["sg_specular_rgb"])
+        ret["indir_rgb"] = lin_diff_combine(ret["indir_diffuse_rgb"], albedo, ret["indir_specular_rgb"])
         supervise = ret["supervise"] + ((mat["sg_normal_map"] - normal_new) ** 2).mean()
         ret.update({"normals": normals, "diffuse_albedo": albedo, "roughness": mat["sg_roughness"],
                     "metallic": mat["sg_metallic"], "normal_map": normal_new, "gradient_error": supervise,

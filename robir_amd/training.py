@@ -20,7 +20,12 @@ IDRNetwork.trace_radiance's pred_vis carries that graph; visibility_loss restate
 The stage's other optimiser step (training/train_visibility.py:309-313) trains indirect_illum_network: enable_illumination_training marks an
 IndirctIllumNetwork.  With the mark, grad mode on and a parameter that requires grad, IndirctIllumNetwork.forward returns (lgt_sgs, env_int)
 with a graph to lobe_layer and integral_layer (robir_amd/illum_autograd.py -> librobir_hip_illumtrain.so, librobir_hip_train.so), the model's
-indirect_sgs / indir_integral carry it, and radiance_loss restates model/loss.py:156-171 on the fused, differentiable query_indir_illum."""
+indirect_sgs / indir_integral carry it, and radiance_loss restates model/loss.py:156-171 on the fused, differentiable query_indir_illum.
+
+The CESR stage (training/train_cesr.py:107-117: the optimiser holds shadow_net and normal_net): enable_cesr_training marks an SDFNetwork of
+kind shadow or normal.  With the mark, grad mode on and a parameter that requires grad, SDFNetwork.forward / eval_point_labels / diffuse_vis /
+unit_normal return outputs with a graph to the 27 weight-norm tensors (robir_amd/cesr_autograd.py -> librobir_hip_cesrtrain.so), and
+renderer.CESRHook carries it into the shading (diffuse_vis) and into the normal-consistency term of gradient_error (normal_new)."""
 import torch
 
 from . import nets
@@ -110,6 +115,22 @@ def visibility_loss(pred_vis, gt_vis, points_mask):
     pred = pred_vis[mask].reshape(-1, 2)
     gt = (~gt_vis[mask].bool()).long().reshape(-1)
     return torch.nn.functional.cross_entropy(pred, gt)
+
+
+def enable_cesr_training(net, on=True):
+    """Mark (on=False: unmark) an SDFNetwork of kind shadow or normal -- the CESR stage's shadow_net / normal_net -- as trainable on the HIP
+    path.  Returns the network.  The NeuS-shape SDFNetwork is refused: its backward is not built."""
+    if not isinstance(net, nets.SDFNetwork):
+        raise TypeError(f"enable_cesr_training: {type(net).__name__} is not an SDFNetwork")
+    if net.kind == "neus":
+        raise NotImplementedError("enable_cesr_training: the backward of the NeuS-shape SDFNetwork (3 -> 257, 256 x 8) is not built -- only "
+                                  "the CESR stage's shadow_net (191 -> 2) and normal_net (63 -> 3) train on the HIP path")
+    net._cesr_training = bool(on)
+    return net
+
+
+def cesr_training_enabled(net):
+    return isinstance(net, nets.SDFNetwork) and bool(getattr(net, "_cesr_training", False))
 
 
 def _illumination_network(obj):
