@@ -3,50 +3,40 @@
 // rejoining before layer 4 as [h | x] / sqrt(2); shadow_net (191 -> 2) and normal_net (63 -> 3) of training/train_cesr.py:107-110.
 //
 // vistrain/vis_bwd.hip's and illumtrain/illum_bwd.hip's shape of problem on the same engine (k_gemm64 of ../train/gemm64.h, instantiated
-// here for the softplus-100 family with per-partition partials): everything is fp64, the encoding is evaluated in double from the fp32
-// coordinates, the activations are recomputed, each stored gradient is rounded once.  This file holds what is particular: the weight-norm
-// fold (k_wnorm) and its reverse (k_finish_wn), k_encode / k_rows / k_skip_fill, k_head_bwd, k_reduce, the plan and the slab loop.
+// here for the softplus-100 family with per-partition partials) under the same slab driver (../train/chain.h): everything is fp64, the
+// encoding is evaluated in double from the fp32 coordinates, the activations are recomputed, each stored gradient is rounded once.  This
+// file holds what is particular: the weight-norm fold (k_wnorm, tree_sum) and its reverse (k_finish_wn), k_encode / k_rows / k_skip_fill,
+// k_head_bwd, the plan, the argument checks and the order of the slab loop.
 //
 // The skip layer: A[3] is a 512-wide buffer whose first 512 - d_in columns layer 3 writes and whose last d_in columns hold x, so layer 4
 // reads [h | x] as it stands; the 1/sqrt(2) sits in the folded W_4 (the same function), comes back into dW_4 in k_finish_wn, and dZ_3 is
 // the product with W_4's first 512 - d_in columns only.
 //
-// Reductions over rows are DESIGN 4.5's: a slab's row range is cut into contiguous partitions of part_rows rows, one workgroup per (output
-// tile, partition) stores an fp64 partial with plain vector stores, k_reduce adds the partials in partition order, slabs add in slab order.
-// No atomics: the association is a function of (M, slab_rows, part_rows) alone.
+// Reductions over rows are DESIGN 4.5's (wgrad_parts of chain.h): no atomics, the association is a function of (M, slab_rows, part_rows)
+// alone.
 #include "../../../include/robir_hip_cesrtrain.h"
-#include "../train/gemm64.h"
+#include "../train/chain.h"
 
 namespace {
 
 constexpr int HID = 512, PE = 63, LABELS = 128, X_LD = 192, RAW_LD = 8, NL = 9, SKIP = 4;
-constexpr long PART_ELEMS = (long)HID * (HID + 1);      // the widest weight gradient with its bias column: one partial
-constexpr int Z_GROUP = 4096;                 // partitions per launch of the weight-gradient GEMM (grid.z)
 constexpr double RSQRT2 = 0.70710678118654752440;
 constexpr int WT = 256;                       // lanes of a weight-norm workgroup: one workgroup owns one output row
 
-constexpr auto gemm = launch_gemm<ACT_SOFTPLUS100_OPT, RED_PART>;      // softplus-100 where Gemm::act is set (the raw output has none)
+// softplus-100 where the act flag is set (the raw output has none); weight gradients leave as per-partition partials (k_reduce)
+constexpr auto fwd = fwd_layer<ACT_SOFTPLUS100_OPT, RED_PART>;
+constexpr auto wgrad = wgrad_parts<ACT_SOFTPLUS100_OPT, RED_PART>;
+constexpr auto bwd = dgrad<ACT_SOFTPLUS100_OPT, RED_PART>;
 
-// X[i, :] of the points form, i < S, row stride ld: column c < 63 is PE10 of point (row0 + i) / n_label -- x_c for c < 3, else with
-// j = c - 3, k = j / 6: sin(2^k x_{j % 6}) for j % 6 < 3, cos(2^k x_{j % 6 - 3}) otherwise (the oracle's encoding.pe, rb_feat_pe10's layout;
-// x 2^k is exact in double) -- and, kind 1, column 63 + j is 1 where j == (row0 + i) % n_label, else 0: built from the row index
+// X[i, :] of the points form, i < S, row stride ld: column c < 63 is PE10 of point (row0 + i) / n_label (pe10_col) and, kind 1, column
+// 63 + j is 1 where j == (row0 + i) % n_label, else 0: built from the row index
 __global__ void k_encode(const float* points, long row0, long S, int n_label, int d_in, int ld, double* X) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S * d_in) return;
     const long row = i / d_in, grow = row0 + row;
     const int c = (int)(i % d_in);
     const float* src = points + (grow / n_label) * 3;
-    double v;
-    if (c >= PE) {
-        v = c - PE == (int)(grow % n_label) ? 1.0 : 0.0;
-    } else if (c < 3) {
-        v = (double)src[c];
-    } else {
-        const int j = c - 3, k = j / 6, r = j % 6;
-        const double a = (double)src[r % 3] * (double)(1 << k);
-        v = r < 3 ? sin(a) : cos(a);
-    }
-    X[row * ld + c] = v;
+    X[row * ld + c] = c >= PE ? (c - PE == (int)(grow % n_label) ? 1.0 : 0.0) : pe10_col(src, c);
 }
 
 // the dense form: X[i, c] = rows[(row0 + i) rows_ld + c], c < d_in
@@ -143,15 +133,6 @@ __global__ void k_head_bwd(const double* raw, const float* g_out, long S, int d_
     }
 }
 
-// acc[e] (+)= partial[0][e] + partial[1][e] + ... in partition order; first = 1: the slab stores, else it adds to what the earlier slabs left
-__global__ void k_reduce(const double* partial, int nparts, long stride, long count, double* acc, int first) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    double s = first ? 0.0 : acc[e];
-    for (int q = 0; q < nparts; ++q) s += partial[(long)q * stride + e];
-    acc[e] = s;
-}
-
 struct Plan {
     long W[NL], acc_off[NL];      // doubles
     long nparts;                  // partitions of a full slab
@@ -165,7 +146,7 @@ Plan make_plan(long S, long part_rows) {
     for (int l = 0; l < NL; ++l) p.W[l] = take(l == 0 ? (long)HID * X_LD : l == 8 ? 3L * HID : (long)HID * HID);
     for (int l = 0; l < NL; ++l) p.acc_off[l] = take(l == 0 ? (long)HID * X_LD : l == 8 ? 3L * (HID + 1) : (long)HID * (HID + 1));
     p.nparts = (S + part_rows - 1) / part_rows;
-    p.partial = take(p.nparts * PART_ELEMS);
+    p.partial = take(p.nparts * PART_ELEMS<HID>);
     p.X = take(S * X_LD);
     for (int l = 0; l < 8; ++l) p.A[l] = take(S * HID);
     p.raw = take(S * RAW_LD);
@@ -173,13 +154,6 @@ Plan make_plan(long S, long part_rows) {
     p.dZ[1] = take(S * HID);
     p.total = take.o;
     return p;
-}
-
-bool check_dims(long M, long slab_rows, long part_rows) {
-    if (M < 0) return fail("M = %ld is negative", M), false;
-    if (slab_rows < 1 || slab_rows > (1L << 20)) return fail("slab_rows = %ld outside [1, 2^20]", slab_rows), false;
-    if (part_rows < 1 || part_rows > slab_rows) return fail("part_rows = %ld outside [1, slab_rows = %ld]", part_rows, slab_rows), false;
-    return true;
 }
 
 }  // namespace
@@ -191,15 +165,14 @@ int rb_ct_abi_version(void) { return RB_CT_ABI_VERSION; }
 const char* rb_ct_last_error(void) { return g_err; }
 
 long rb_ct_cesr_bwd_scratch_bytes(long M, long slab_rows, long part_rows) {
-    if (!check_dims(M, slab_rows, part_rows)) return -1;
-    const long S = M < slab_rows ? (M > 0 ? M : 1) : slab_rows;
-    return make_plan(S, part_rows).total * (long)sizeof(double);
+    if (!check_rows("M", M, slab_rows, part_rows)) return -1;
+    return make_plan(query_slab_size(M, slab_rows), part_rows).total * (long)sizeof(double);
 }
 
 int rb_ct_cesr_bwd(const float* points, const float* rows, long ld, long M, int kind, int n_label, int head, const float* const* params,
                    const float* g_out, float* const* grads, long slab_rows, long part_rows, void* scratch, long scratch_bytes, int* stats,
                    rb_ct_stream_t stream) {
-    if (!check_dims(M, slab_rows, part_rows)) return 1;
+    if (!check_rows("M", M, slab_rows, part_rows)) return 1;
     if (kind != 0 && kind != 1) return fail("kind = %d: 0 normal_net (63 -> 3), 1 shadow_net (191 -> 2)", kind);
     if (head < 0 || head > 2 || (head == 1 && kind != 1) || (head == 2 && kind != 0))
         return fail("head = %d with kind = %d: 0 raw output, 1 softmax class-1 probability (kind 1 only), 2 unit vector (kind 0 only)", head, kind);
@@ -216,13 +189,9 @@ int rb_ct_cesr_bwd(const float* points, const float* rows, long ld, long M, int 
     for (int i = 0; i < 3 * NL; ++i)
         if (!params[i]) return fail("null pointer: params[%d]", i);
     bool want_layer[NL];
-    int lowest = NL;                                  // first layer that wants a gradient: the data path stops there
-    for (int l = NL - 1; l >= 0; --l) {
-        want_layer[l] = grads[3 * l] || grads[3 * l + 1] || grads[3 * l + 2];
-        if (want_layer[l]) lowest = l;
-    }
+    const int lowest = scan_wanted(grads, NL, 3, want_layer);      // first layer that wants a gradient: the data path stops there
     if (lowest == NL) return 0;
-    const long S0 = M < slab_rows ? M : slab_rows;
+    const long S0 = slab_size(M, slab_rows);
     const Plan pl = make_plan(S0, part_rows);
     if (check_scratch(scratch, scratch_bytes, pl.total * (long)sizeof(double), "rb_ct_cesr_bwd_scratch_bytes")) return 1;
     hipStream_t st = (hipStream_t)stream;
@@ -250,18 +219,8 @@ int rb_ct_cesr_bwd(const float* points, const float* rows, long ld, long M, int 
             hipLaunchKernelGGL(k_rows, ew_grid(S * d_in), dim3(256), 0, st, rows, ld, row0, S, d_in, in_ld, D + pl.X);
         hipLaunchKernelGGL(k_skip_fill, ew_grid(S * d_in), dim3(256), 0, st, D + pl.X, in_ld, S, d_in, D + pl.A[3]);
         g_launches += 2;
-        for (int l = 0; l < NL; ++l) {
-            const Layer& L = LAYERS[l];
-            Gemm g{};
-            g.A = in[l]; g.sam = L.in_ld; g.sak = 1; g.a_f32 = 0;
-            g.B = D + pl.W[l]; g.sbk = 1; g.sbn = L.k_in; g.b_f32 = 0;
-            g.ones_col = -1;
-            g.M = (int)S; g.N = L.n_out; g.K = L.k_in;
-            g.epi = EPI_FWD; g.bias = G[3 * l + 2];
-            g.act = l < 8;
-            g.C = l < 8 ? D + pl.A[l] : D + pl.raw; g.ldc = l < 8 ? HID : RAW_LD;
-            bad |= gemm(g, 1, st);
-        }
+        for (int l = 0; l < NL; ++l)
+            bad |= fwd(LAYERS[l], S, in[l], 0, D + pl.W[l], 0, G[3 * l + 2], l < 8, l < 8 ? D + pl.A[l] : D + pl.raw, l < 8 ? HID : RAW_LD, st);
         // d loss / d (pre-activation of layer l) sits in dz [S, dz_ld]: the head's derivative for the last layer (dZ[1], d_out wide)
         const long g_w = head == 1 ? 1 : d_out;
         hipLaunchKernelGGL(k_head_bwd, ew_grid(S), dim3(256), 0, st, D + pl.raw, g_out + row0 * g_w, S, d_out, head, D + pl.dZ[1]);
@@ -270,35 +229,11 @@ int rb_ct_cesr_bwd(const float* points, const float* rows, long ld, long M, int 
         long dz_ld = d_out;
         for (int l = NL - 1; l >= lowest; --l) {
             const Layer& L = LAYERS[l];
-            if (want_layer[l]) {
-                const long count = (long)L.n_out * (L.k_in + 1);
-                const int nparts = (int)((S + part_rows - 1) / part_rows);
-                Gemm g{};
-                g.A = dz; g.sam = 1; g.sak = dz_ld; g.a_f32 = 0;                    // A(m = neuron, k = row)
-                g.B = in[l]; g.sbk = L.in_ld; g.sbn = 1; g.b_f32 = 0;               // B(k = row, n = input column)
-                g.ones_col = L.k_in;
-                g.M = L.n_out; g.N = L.k_in + 1; g.K = (int)S;
-                g.epi = EPI_WGRAD; g.C = D + pl.partial; g.ldc = L.k_in + 1;
-                g.part_rows = (int)part_rows; g.part_stride = count;
-                for (int q0 = 0; q0 < nparts; q0 += Z_GROUP) {
-                    g.part0 = q0;
-                    bad |= gemm(g, nparts - q0 < Z_GROUP ? nparts - q0 : Z_GROUP, st);
-                }
-                hipLaunchKernelGGL(k_reduce, ew_grid(count), dim3(256), 0, st, D + pl.partial, nparts, count, count, D + pl.acc_off[l], first);
-                ++g_launches;
-            }
+            if (want_layer[l]) bad |= wgrad(L, S, dz, 0, dz_ld, in[l], part_rows, D + pl.partial, D + pl.acc_off[l], first, st);
             if (l > lowest) {
                 // dZ_{l-1} = (dZ_l W_l) . gate(A_{l-1}); the skip layer: into the first 512 - d_in of its input columns only
-                const int n_prev = LAYERS[l - 1].n_out;
                 double* to = D + pl.dZ[l & 1];
-                Gemm g{};
-                g.A = dz; g.sam = dz_ld; g.sak = 1; g.a_f32 = 0;
-                g.B = D + pl.W[l]; g.sbk = L.k_in; g.sbn = 1; g.b_f32 = 0;
-                g.ones_col = -1;
-                g.M = (int)S; g.N = n_prev; g.K = L.n_out;
-                g.epi = EPI_BWD; g.C = to; g.ldc = HID;
-                g.act = 1; g.mask = in[l]; g.ldm = HID;
-                bad |= gemm(g, 1, st);
+                bad |= bwd(L, S, dz, 0, dz_ld, D + pl.W[l], 0, LAYERS[l - 1].n_out, 1, in[l], to, st);
                 dz = to;
                 dz_ld = HID;
             }

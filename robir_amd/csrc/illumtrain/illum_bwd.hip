@@ -3,45 +3,34 @@
 // spherical-Gaussian query of model/loss.py:128-141 with its reverse.
 //
 // The lobe net is vistrain/vis_bwd.hip's shape of problem and runs on the same engine (k_gemm64 of ../train/gemm64.h, instantiated here for
-// the family with one layer that has no activation -- the raw output the head reads -- and per-partition partials): everything is fp64, the
-// encoding is evaluated in double from the fp32 coordinates, the activations are recomputed, each stored gradient is rounded once
-// (k_finish).  This file holds what is particular: k_encode, k_head_bwd, k_reduce, the plan and the slab loop, and the two query kernels.
+// the family with one layer that has no activation -- the raw output the head reads -- and per-partition partials) under the same slab
+// driver (../train/chain.h): everything is fp64, the encoding is evaluated in double from the fp32 coordinates, the activations are
+// recomputed, each stored gradient is rounded once (k_finish).  This file holds what is particular: k_encode, k_head_bwd, the plan, the
+// argument checks and the order of the slab loop, and the two query kernels.
 //
-// Reductions over rows are DESIGN 4.5's: a slab's row range is cut into contiguous partitions of part_rows rows, one workgroup per (output
-// tile, partition) stores an fp64 partial with plain vector stores, k_reduce adds the partials in partition order, slabs add in slab order.
-// No atomics: the association is a function of (n, slab_rows, part_rows) alone.
+// Reductions over rows are DESIGN 4.5's (wgrad_parts of chain.h): no atomics, the association is a function of (n, slab_rows, part_rows)
+// alone.
 #include "../../../include/robir_hip_illumtrain.h"
-#include "../train/gemm64.h"
+#include "../train/chain.h"
 
 namespace {
 
 constexpr int HID = 512, IN_LD = 64, PE = 63, LOBES = 24, RAW = LOBES * 6, SG = 7;
-constexpr long PART_ELEMS = (long)HID * (HID + 1);      // the widest weight gradient with its bias column: one partial
-constexpr int Z_GROUP = 4096;                 // partitions per launch of the weight-gradient GEMM (grid.z)
 constexpr double PI = 3.14159265358979323846;
 
-constexpr auto gemm = launch_gemm<ACT_RELU_OPT, RED_PART>;      // ReLU where Gemm::act is set (the raw output has none); per-partition partials
+// ReLU where the act flag is set (the raw output has none); weight gradients leave as per-partition partials (k_reduce)
+constexpr auto fwd = fwd_layer<ACT_RELU_OPT, RED_PART>;
+constexpr auto wgrad = wgrad_parts<ACT_RELU_OPT, RED_PART>;
+constexpr auto bwd = dgrad<ACT_RELU_OPT, RED_PART>;
 
-// X[i, :] = [PE10(points[row0 + i]) | hdr[row0 + i]], i < S: column c is x_c for c < 3, else with j = c - 3, k = j / 6: sin(2^k x_{j % 6})
-// for j % 6 < 3, cos(2^k x_{j % 6 - 3}) otherwise (the oracle's encoding.pe, rb_feat_pe10's layout); column 63 is the hdr shift, 0 without
-// one.  x 2^k is exact in double.
+// X[i, :] = [PE10(points[row0 + i]) | hdr[row0 + i]], i < S (pe10_col: a column of PE10); column 63 is the hdr shift, 0 without one
 __global__ void k_encode(const float* points, const float* hdr, long row0, long S, double* X) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S * IN_LD) return;
     const long row = i / IN_LD;
     const int c = (int)(i % IN_LD);
     const float* src = points + (row0 + row) * 3;
-    double v;
-    if (c == PE) {
-        v = hdr ? (double)hdr[row0 + row] : 0.0;
-    } else if (c < 3) {
-        v = (double)src[c];
-    } else {
-        const int j = c - 3, k = j / 6, r = j % 6;
-        const double a = (double)src[r % 3] * (double)(1 << k);
-        v = r < 3 ? sin(a) : cos(a);
-    }
-    X[i] = v;
+    X[i] = c == PE ? (hdr ? (double)hdr[row0 + row] : 0.0) : pe10_col(src, c);
 }
 
 __device__ __forceinline__ double sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
@@ -65,15 +54,6 @@ __global__ void k_head_bwd(const double* raw, const float* g_sgs, long S, double
     for (int c = 0; c < 3; ++c) o[3 + c] = z[3 + c] > 0.0 ? (double)g[4 + c] : 0.0;
 }
 
-// acc[e] (+)= partial[0][e] + partial[1][e] + ... in partition order; first = 1: the slab stores, else it adds to what the earlier slabs left
-__global__ void k_reduce(const double* partial, int nparts, long stride, long count, double* acc, int first) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    double s = first ? 0.0 : acc[e];
-    for (int q = 0; q < nparts; ++q) s += partial[(long)q * stride + e];
-    acc[e] = s;
-}
-
 struct Plan {
     long acc_off[5];          // doubles
     long nparts;              // partitions of a full slab
@@ -88,7 +68,7 @@ Plan make_plan(long S, long part_rows) {
     for (int l = 1; l < 4; ++l) p.acc_off[l] = take((long)HID * (HID + 1));
     p.acc_off[4] = take((long)RAW * (HID + 1));
     p.nparts = (S + part_rows - 1) / part_rows;
-    p.partial = take(p.nparts * PART_ELEMS);
+    p.partial = take(p.nparts * PART_ELEMS<HID>);
     p.X = take(S * IN_LD);
     for (int l = 0; l < 4; ++l) p.A[l] = take(S * HID);
     p.raw = take(S * RAW);
@@ -96,13 +76,6 @@ Plan make_plan(long S, long part_rows) {
     p.dZ[1] = take(S * HID);
     p.total = take.o;
     return p;
-}
-
-bool check_dims(long n, long slab_rows, long part_rows) {
-    if (n < 0) return fail("n = %ld is negative", n), false;
-    if (slab_rows < 1 || slab_rows > (1L << 20)) return fail("slab_rows = %ld outside [1, 2^20]", slab_rows), false;
-    if (part_rows < 1 || part_rows > slab_rows) return fail("part_rows = %ld outside [1, slab_rows = %ld]", part_rows, slab_rows), false;
-    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the SG query
@@ -202,25 +175,23 @@ int rb_it_abi_version(void) { return RB_IT_ABI_VERSION; }
 const char* rb_it_last_error(void) { return g_err; }
 
 long rb_it_lobe_bwd_scratch_bytes(long n, long slab_rows, long part_rows) {
-    if (!check_dims(n, slab_rows, part_rows)) return -1;
-    const long S = n < slab_rows ? (n > 0 ? n : 1) : slab_rows;
-    return make_plan(S, part_rows).total * (long)sizeof(double);
+    if (!check_rows("n", n, slab_rows, part_rows)) return -1;
+    return make_plan(query_slab_size(n, slab_rows), part_rows).total * (long)sizeof(double);
 }
 
 int rb_it_lobe_bwd(const float* points, const float* hdr, long n, const float* const* params, const float* g_sgs, float* const* grads,
                    long slab_rows, long part_rows, void* scratch, long scratch_bytes, int* stats, rb_it_stream_t stream) {
-    if (!check_dims(n, slab_rows, part_rows)) return 1;
+    if (!check_rows("n", n, slab_rows, part_rows)) return 1;
     if (!params || !grads) return fail("null pointer: params / grads (HOST arrays of 10 device pointers)");
     if (stats) { stats[0] = 0; stats[1] = 5; stats[2] = 0; }
     if (n == 0) return 0;
     if (!points || !g_sgs) return fail("null pointer: points / g_sgs");
     for (int i = 0; i < 10; ++i)
         if (!params[i]) return fail("null pointer: params[%d]", i);
-    int lowest = 5;                                   // first layer that wants a gradient: the data path stops there
-    for (int l = 4; l >= 0; --l)
-        if (grads[2 * l] || grads[2 * l + 1]) lowest = l;
+    bool want_layer[5];
+    const int lowest = scan_wanted(grads, 5, 2, want_layer);      // first layer that wants a gradient: the data path stops there
     if (lowest == 5) return 0;
-    const long S0 = n < slab_rows ? n : slab_rows;
+    const long S0 = slab_size(n, slab_rows);
     const Plan pl = make_plan(S0, part_rows);
     if (check_scratch(scratch, scratch_bytes, pl.total * (long)sizeof(double), "rb_it_lobe_bwd_scratch_bytes")) return 1;
     hipStream_t st = (hipStream_t)stream;
@@ -229,8 +200,6 @@ int rb_it_lobe_bwd(const float* points, const float* hdr, long n, const float* c
     int bad = 0;
     // the no_hdr net has no weight column for the hdr shift: W0 is [512, 63] and column 63 of X is never read
     const Layer LAYERS[5] = {{HID, hdr ? IN_LD : PE, IN_LD}, {HID, HID, HID}, {HID, HID, HID}, {HID, HID, HID}, {RAW, HID, HID}};
-    bool want_layer[5];
-    for (int l = 0; l < 5; ++l) want_layer[l] = grads[2 * l] || grads[2 * l + 1];
 
     for (long row0 = 0; row0 < n; row0 += S0) {
         const long S = n - row0 < S0 ? n - row0 : S0;
@@ -238,52 +207,21 @@ int rb_it_lobe_bwd(const float* points, const float* hdr, long n, const float* c
         const double* in[5] = {D + pl.X, D + pl.A[0], D + pl.A[1], D + pl.A[2], D + pl.A[3]};      // input rows of layer l
         hipLaunchKernelGGL(k_encode, ew_grid(S * IN_LD), dim3(256), 0, st, points, hdr, row0, S, D + pl.X);
         ++g_launches;
-        for (int l = 0; l < 5; ++l) {
-            const Layer& L = LAYERS[l];
-            Gemm g{};
-            g.A = in[l]; g.sam = L.in_ld; g.sak = 1; g.a_f32 = 0;
-            g.B = params[2 * l]; g.sbk = 1; g.sbn = L.k_in; g.b_f32 = 1;
-            g.ones_col = -1;
-            g.M = (int)S; g.N = L.n_out; g.K = L.k_in;
-            g.epi = EPI_FWD; g.bias = params[2 * l + 1];
-            g.act = l < 4;
-            g.C = l < 4 ? D + pl.A[l] : D + pl.raw; g.ldc = L.n_out;
-            bad |= gemm(g, 1, st);
-        }
-        // d loss / d (pre-activation of layer l) sits in dz [S, n_out]: the head's derivative for the last layer (dZ[1], 144 wide)
+        for (int l = 0; l < 5; ++l)
+            bad |= fwd(LAYERS[l], S, in[l], 0, params[2 * l], 1, params[2 * l + 1], l < 4, l < 4 ? D + pl.A[l] : D + pl.raw, LAYERS[l].n_out, st);
+        // d loss / d (pre-activation of layer l) sits in dz [S, dz_ld]: the head's derivative for the last layer (dZ[1], 144 wide)
         hipLaunchKernelGGL(k_head_bwd, ew_grid(S * LOBES), dim3(256), 0, st, D + pl.raw, g_sgs + row0 * LOBES * SG, S, D + pl.dZ[1]);
         ++g_launches;
         const double* dz = D + pl.dZ[1];
+        long dz_ld = RAW;
         for (int l = 4; l >= lowest; --l) {
             const Layer& L = LAYERS[l];
-            if (want_layer[l]) {
-                const long count = (long)L.n_out * (L.k_in + 1);
-                const int nparts = (int)((S + part_rows - 1) / part_rows);
-                Gemm g{};
-                g.A = dz; g.sam = 1; g.sak = L.n_out; g.a_f32 = 0;                  // A(m = neuron, k = row)
-                g.B = in[l]; g.sbk = L.in_ld; g.sbn = 1; g.b_f32 = 0;               // B(k = row, n = input column)
-                g.ones_col = L.k_in;
-                g.M = L.n_out; g.N = L.k_in + 1; g.K = (int)S;
-                g.epi = EPI_WGRAD; g.C = D + pl.partial; g.ldc = L.k_in + 1;
-                g.part_rows = (int)part_rows; g.part_stride = count;
-                for (int q0 = 0; q0 < nparts; q0 += Z_GROUP) {
-                    g.part0 = q0;
-                    bad |= gemm(g, nparts - q0 < Z_GROUP ? nparts - q0 : Z_GROUP, st);
-                }
-                hipLaunchKernelGGL(k_reduce, ew_grid(count), dim3(256), 0, st, D + pl.partial, nparts, count, count, D + pl.acc_off[l], first);
-                ++g_launches;
-            }
+            if (want_layer[l]) bad |= wgrad(L, S, dz, 0, dz_ld, in[l], part_rows, D + pl.partial, D + pl.acc_off[l], first, st);
             if (l > lowest) {
                 double* to = D + pl.dZ[l & 1];
-                Gemm g{};
-                g.A = dz; g.sam = L.n_out; g.sak = 1; g.a_f32 = 0;
-                g.B = params[2 * l]; g.sbk = L.k_in; g.sbn = 1; g.b_f32 = 1;
-                g.ones_col = -1;
-                g.M = (int)S; g.N = L.k_in; g.K = L.n_out;
-                g.epi = EPI_BWD; g.C = to; g.ldc = HID;
-                g.act = 1; g.mask = in[l]; g.ldm = HID;
-                bad |= gemm(g, 1, st);
+                bad |= bwd(L, S, dz, 0, dz_ld, params[2 * l], 1, L.k_in, 1, in[l], to, st);
                 dz = to;
+                dz_ld = HID;
             }
         }
     }

@@ -2,20 +2,24 @@
 //
 // Everything is fp64: the layer activations are recomputed from the fp32 feature rows and the fp32 nn.Linear parameters, the three product
 // families (activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ) run on v_mfma_f64_16x16x4_f64 through the training libraries' one
-// tiled kernel (k_gemm64 of gemm64.h, instantiated here for LeakyReLU(0.2) and in-place accumulation), and each stored gradient is rounded
-// to fp32 once (k_finish).  This file holds what is particular to the auto-encoder: its element-wise kernels, its plan and its slab loop.
+// tiled kernel (k_gemm64 of gemm64.h, instantiated here for LeakyReLU(0.2) and in-place accumulation) under the slab driver the four
+// training libraries share (chain.h), and each stored gradient is rounded to fp32 once (k_finish).  This file holds what is particular to
+// the auto-encoder: its latent and output kernels, its plan, its argument checks and the two-pass order of its slab loop.
 //
 // Reductions over rows: dW / db of a layer is a GEMM whose REDUCTION dimension is the slab's rows; one thread owns one element of the fp64
-// accumulator (no atomics, no split over rows), slabs are enqueued in order on one stream and add into that element in slab order.  The
-// accumulation order is therefore a function of (n, slab_rows) alone.
+// accumulator (no atomics, no split over rows: wgrad_acc of chain.h), slabs are enqueued in order on one stream and add into that element
+// in slab order.  The accumulation order is therefore a function of (n, slab_rows) alone.
 //
 // The decoder's two passes (clean latent | latent + noise * scale) are stacked as 2 S rows of one problem: their weight gradients are one sum.
 #include "../../../include/robir_hip_train.h"
-#include "gemm64.h"
+#include "chain.h"
 
 namespace {
 
-constexpr auto gemm = launch_gemm<ACT_LEAKY, RED_ACC>;      // LeakyReLU(0.2) hidden layers; weight gradients add in place, slab by slab
+// LeakyReLU(0.2) where the act flag is set; weight gradients add in place, slab by slab
+constexpr auto fwd = fwd_layer<ACT_LEAKY, RED_ACC>;
+constexpr auto wgrad = wgrad_acc<ACT_LEAKY, RED_ACC>;
+constexpr auto bwd = dgrad<ACT_LEAKY, RED_ACC>;
 
 __device__ __forceinline__ double sigmoid64(double x) { return 1.0 / (1.0 + exp(-x)); }
 
@@ -100,8 +104,7 @@ Plan make_plan(long S, int in_dim, int od) {
 }
 
 bool check_dims(long n, long slab_rows, int in_dim, int out_dim) {
-    if (n < 0) return fail("n = %ld is negative", n), false;
-    if (slab_rows < 1 || slab_rows > (1L << 20)) return fail("slab_rows = %ld outside [1, 2^20]", slab_rows), false;
+    if (!check_rows("n", n, slab_rows)) return false;
     if (in_dim < 1 || in_dim > 64) return fail("in_dim = %d outside [1, 64]", in_dim), false;
     if (out_dim < 1 || out_dim > 16) return fail("out_dim = %d outside [1, 16]", out_dim), false;
     return true;
@@ -117,8 +120,7 @@ const char* rb_train_last_error(void) { return g_err; }
 
 long rb_train_ae_bwd_scratch_bytes(long n, long slab_rows, int in_dim, int out_dim) {
     if (!check_dims(n, slab_rows, in_dim, out_dim)) return -1;
-    const long S = n < slab_rows ? (n > 0 ? n : 1) : slab_rows;
-    return make_plan(S, in_dim, out_dim).total * (long)sizeof(double);
+    return make_plan(query_slab_size(n, slab_rows), in_dim, out_dim).total * (long)sizeof(double);
 }
 
 int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, double noise_scale, const float* var, int latent_act, int out_act,
@@ -133,21 +135,17 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
     if (!X) return fail("null pointer: X");
     for (int i = 0; i < 16; ++i)
         if (!params[i]) return fail("null pointer: params[%d]", i);
-    bool any = false, enc = false;
-    int lowest = 8;                                   // first layer that wants a gradient: the data path stops there
-    for (int l = 7; l >= 0; --l)
-        if (grads[2 * l] || grads[2 * l + 1]) { any = true; lowest = l; }
-    enc = lowest < 5;
-    if (!any) return 0;
-    const long S0 = n < slab_rows ? n : slab_rows;
+    bool want_layer[8];
+    const int lowest = scan_wanted(grads, 8, 2, want_layer);      // first layer that wants a gradient: the data path stops there
+    if (lowest == 8) return 0;
+    const bool enc = lowest < 5;
+    const long S0 = slab_size(n, slab_rows);
     const Plan p = make_plan(S0, in_dim, out_dim);
     if (check_scratch(scratch, scratch_bytes, p.total * (long)sizeof(double), "rb_train_ae_bwd_scratch_bytes")) return 1;
     hipStream_t st = (hipStream_t)stream;
     double* D = (double*)scratch;
     g_launches = 0;
     int bad = 0;
-    const bool want_layer[8] = {grads[0] || grads[1], grads[2] || grads[3], grads[4] || grads[5], grads[6] || grads[7],
-                                grads[8] || grads[9], grads[10] || grads[11], grads[12] || grads[13], grads[14] || grads[15]};
 
     for (long row0 = 0; row0 < n; row0 += S0) {
         const long S = n - row0 < S0 ? n - row0 : S0;
@@ -157,38 +155,13 @@ int rb_train_ae_bwd(const float* X, long n, int in_dim, const float* noise, doub
         const void* in[8] = {Xs, D + p.A[0], D + p.A[1], D + p.A[2], D + p.A[3], D + p.LAT, D + p.H[0], D + p.H[1]};
         double* out[8] = {D + p.A[0], D + p.A[1], D + p.A[2], D + p.A[3], D + p.RAW, D + p.H[0], D + p.H[1], D + p.Z};
         auto forward = [&](int l, long M) {
-            const Layer& L = p.L[l];
-            Gemm g{};
-            g.A = in[l]; g.sam = L.in_ld; g.sak = 1; g.a_f32 = l == 0;
-            g.B = params[2 * l]; g.sbk = 1; g.sbn = L.k_in; g.b_f32 = 1;
-            g.ones_col = -1;
-            g.M = (int)M; g.N = L.n_out; g.K = L.k_in;
-            g.epi = EPI_FWD; g.C = out[l]; g.ldc = L.n_out; g.bias = params[2 * l + 1];
-            g.act = l != 4 && l != 7;
-            bad |= gemm(g, 1, st);
+            bad |= fwd(p.L[l], M, in[l], l == 0, params[2 * l], 1, params[2 * l + 1], l != 4 && l != 7, out[l], p.L[l].n_out, st);
         };
         // d loss / d (pre-activation of layer l) sits in dz [M, n_out]: accumulate dW | db, and (to != NULL) hand the gradient to layer l - 1
         auto backward = [&](int l, long M, const double* dz, double* to, bool mask_prev) {
             const Layer& L = p.L[l];
-            if (want_layer[l]) {
-                Gemm g{};
-                g.A = dz; g.sam = 1; g.sak = L.n_out; g.a_f32 = 0;                 // A(m = neuron, k = row)
-                g.B = in[l]; g.sbk = L.in_ld; g.sbn = 1; g.b_f32 = l == 0;          // B(k = row, n = input column)
-                g.ones_col = L.k_in;
-                g.M = L.n_out; g.N = L.k_in + 1; g.K = (int)M;
-                g.epi = EPI_WGRAD; g.C = D + p.acc_off[l]; g.ldc = L.k_in + 1; g.first = first;
-                bad |= gemm(g, 1, st);
-            }
-            if (to) {
-                Gemm g{};
-                g.A = dz; g.sam = L.n_out; g.sak = 1; g.a_f32 = 0;
-                g.B = params[2 * l]; g.sbk = L.k_in; g.sbn = 1; g.b_f32 = 1;
-                g.ones_col = -1;
-                g.M = (int)M; g.N = L.k_in; g.K = L.n_out;
-                g.epi = EPI_BWD; g.C = to; g.ldc = L.k_in;
-                g.act = mask_prev; g.mask = (const double*)in[l]; g.ldm = L.in_ld;
-                bad |= gemm(g, 1, st);
-            }
+            if (want_layer[l]) bad |= wgrad(L, M, dz, L.n_out, in[l], l == 0, D + p.acc_off[l], first, st);
+            if (to) bad |= bwd(L, M, dz, 0, L.n_out, params[2 * l], 1, L.k_in, mask_prev, (const double*)in[l], to, st);
         };
         for (int l = 0; l < 5; ++l) forward(l, S);
         hipLaunchKernelGGL(k_latent, ew_grid(S * 32), dim3(256), 0, st, D + p.RAW, var, noise ? noise + row0 * 32 : nullptr, noise_scale,

@@ -1,8 +1,9 @@
 // The fp64 GEMM engine of the training libraries (librobir_hip_train.so: train/ae_bwd.hip, librobir_hip_vistrain.so: vistrain/vis_bwd.hip,
 // librobir_hip_illumtrain.so: illumtrain/illum_bwd.hip, librobir_hip_cesrtrain.so: cesrtrain/cesr_bwd.hip).  A reverse mode is three product families -- activations, dX = (dY . act') W, dW = dZ^T A | db = sum dZ -- and all of them
 // run on v_mfma_f64_16x16x4_f64 through ONE tiled kernel, k_gemm64, whose operands are addressed by (row stride, column stride).  Included
-// once per library: everything here is internal to the including translation unit (each library keeps its own
-// last-error string and launch counter), and each library instantiates k_gemm64 for the one (activation family, reduction mode) it runs.
+// once per library (through chain.h, the host-side slab driver on top of it): everything here is internal to the including translation
+// unit (each library keeps its own last-error string and launch counter), and each library instantiates k_gemm64 for the one (activation
+// family, reduction mode) it runs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>

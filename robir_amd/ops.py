@@ -488,7 +488,7 @@ def ae_backward(X, params, g_out=None, g_out_xi=None, g_raw=None, noise=None, va
 
 
 def _param_backward(who, names, params, want, *, rows, dev, lib, query, query_args, launch):
-    """The common tail of ae_backward / vis_backward (`who`, for the error text): allocates the gradients named in `want` (a subset of
+    """The common tail of the four *_backward functions (`who`, for the error text): allocates the gradients named in `want` (a subset of
     `names`, the order of `params`) and -- rows > 0 and something wanted -- the fp64 scratch that lib()'s `query` asks for, then runs
     launch(params' pointer array, gradients' pointer array with NULL for the unwanted, scratch, its bytes).  -> (dict name -> gradient,
     scratch bytes)."""
@@ -509,6 +509,19 @@ def _param_backward(who, names, params, want, *, rows, dev, lib, query, query_ar
     return out, nbytes
 
 
+def _partitioned_backward(who, names, params, want, *, rows, dev, lib, query, launch, n_layers, slab_rows, part_rows, defaults):
+    """The common tail of the three row-partitioned backwards: (slab_rows, part_rows) or the module's `defaults`, the library's three-int
+    stats, _param_backward with launch(params' pointer array, gradients' pointer array, `tail`), `tail` being the arguments every such
+    entry point ends in (slab_rows, part_rows, scratch, scratch_bytes, stats, stream), and the stats dict."""
+    slab = int(slab_rows or defaults[0])
+    part = int(part_rows or min(slab, defaults[1]))
+    stats = (c_int * 3)(0, n_layers, 0)
+    out, nbytes = _param_backward(
+        who, names, params, want, rows=rows, dev=dev, lib=lib, query=query, query_args=(c_long(rows), c_long(slab), c_long(part)),
+        launch=lambda P, G, scratch, nbytes: launch(P, G, (c_long(slab), c_long(part), ptr(scratch), c_long(nbytes), stats, stream_ptr())))
+    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+
+
 VIS_PARAM_NAMES = tuple(f"vis_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias"))
 # A full slab's widest weight gradient (256 x 257: 20 output tiles) is 20 * 16384 / 1024 = 320 workgroups on 256 compute units, and the
 # scratch is 227 MB whatever the batch (profiles/vis_backward_times.md)
@@ -527,16 +540,11 @@ def vis_backward(points, dirs, rep, params, g_logits, want=VIS_PARAM_NAMES, slab
     assert dirs.dim() == 2 and dirs.shape[1] == 3 and rep >= 1 and points.shape[0] * rep == M and len(params) == 10
     params = [_f32(p.detach()) for p in params]
     g_logits = _f32(g_logits.detach()).reshape(M, 2)
-    slab = int(slab_rows or VIS_SLAB_ROWS)
-    part = int(part_rows or min(slab, VIS_PART_ROWS))
-    stats = (c_int * 3)(0, 5, 0)
-    out, nbytes = _param_backward(
-        "vis_backward", VIS_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.vistrain, query="rb_vt_vis_bwd_scratch_bytes",
-        query_args=(c_long(M), c_long(slab), c_long(part)),
-        launch=lambda P, G, scratch, nbytes: _lib.call_vistrain(
-            "rb_vt_vis_bwd", ptr(points), ptr(dirs), c_long(M), c_int(rep), P, ptr(g_logits), G, c_long(slab), c_long(part), ptr(scratch),
-            c_long(nbytes), stats, stream_ptr()))
-    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+    return _partitioned_backward(
+        "vis_backward", VIS_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.vistrain, query="rb_vt_vis_bwd_scratch_bytes", n_layers=5,
+        slab_rows=slab_rows, part_rows=part_rows, defaults=(VIS_SLAB_ROWS, VIS_PART_ROWS),
+        launch=lambda P, G, tail: _lib.call_vistrain(
+            "rb_vt_vis_bwd", ptr(points), ptr(dirs), c_long(M), c_int(rep), P, ptr(g_logits), G, *tail))
 
 
 ILLUM_PARAM_NAMES = tuple(f"lobe_layer.{2 * i}.{w}" for i in range(5) for w in ("weight", "bias"))
@@ -560,16 +568,10 @@ def illum_lobe_backward(points, hdr, params, g_sgs, want=ILLUM_PARAM_NAMES, slab
     params = [_f32(p.detach()) for p in params]
     assert tuple(params[0].shape) == (512, 63 if hdr is None else 64), "lobe_layer.0.weight is [512,64] with hdr, [512,63] without"
     g_sgs = _f32(g_sgs.detach()).reshape(n, 24, 7)
-    slab = int(slab_rows or ILLUM_SLAB_ROWS)
-    part = int(part_rows or min(slab, ILLUM_PART_ROWS))
-    stats = (c_int * 3)(0, 5, 0)
-    out, nbytes = _param_backward(
+    return _partitioned_backward(
         "illum_lobe_backward", ILLUM_PARAM_NAMES, params, want, rows=n, dev=dev, lib=_lib.illumtrain, query="rb_it_lobe_bwd_scratch_bytes",
-        query_args=(c_long(n), c_long(slab), c_long(part)),
-        launch=lambda P, G, scratch, nbytes: _lib.call_illumtrain(
-            "rb_it_lobe_bwd", ptr(points), ptr(hdr), c_long(n), P, ptr(g_sgs), G, c_long(slab), c_long(part), ptr(scratch), c_long(nbytes),
-            stats, stream_ptr()))
-    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+        n_layers=5, slab_rows=slab_rows, part_rows=part_rows, defaults=(ILLUM_SLAB_ROWS, ILLUM_PART_ROWS),
+        launch=lambda P, G, tail: _lib.call_illumtrain("rb_it_lobe_bwd", ptr(points), ptr(hdr), c_long(n), P, ptr(g_sgs), G, *tail))
 
 
 CESR_PARAM_NAMES = tuple(f"lin{l}.{w}" for l in range(9) for w in ("weight_g", "weight_v", "bias"))
@@ -597,16 +599,12 @@ def cesr_backward(x, M, kind, params, g_out, head=0, n_label=1, want=CESR_PARAM_
     params = [_f32(p.detach()) for p in params]
     assert tuple(params[1].shape) == (512, d_in) and tuple(params[25].shape) == (d_out, 512), f"not the {kind} network's tensors"
     g_out = _f32(g_out.detach()).reshape((M,) if head == 1 else (M, d_out))
-    slab = int(slab_rows or CESR_SLAB_ROWS)
-    part = int(part_rows or min(slab, CESR_PART_ROWS))
-    stats = (c_int * 3)(0, 9, 0)
-    out, nbytes = _param_backward(
-        "cesr_backward", CESR_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.cesrtrain, query="rb_ct_cesr_bwd_scratch_bytes",
-        query_args=(c_long(M), c_long(slab), c_long(part)),
-        launch=lambda P, G, scratch, nbytes: _lib.call_cesrtrain(
+    return _partitioned_backward(
+        "cesr_backward", CESR_PARAM_NAMES, params, want, rows=M, dev=dev, lib=_lib.cesrtrain, query="rb_ct_cesr_bwd_scratch_bytes", n_layers=9,
+        slab_rows=slab_rows, part_rows=part_rows, defaults=(CESR_SLAB_ROWS, CESR_PART_ROWS),
+        launch=lambda P, G, tail: _lib.call_cesrtrain(
             "rb_ct_cesr_bwd", ptr(x if points else None), ptr(None if points else x), c_long(x.shape[1]), c_long(M), c_int(code),
-            c_int(n_label), c_int(head), P, ptr(g_out), G, c_long(slab), c_long(part), ptr(scratch), c_long(nbytes), stats, stream_ptr()))
-    return out, {"launches": int(stats[0]), "lowest_layer": int(stats[1]), "partitions": int(stats[2]), "scratch_bytes": nbytes}
+            c_int(n_label), c_int(head), P, ptr(g_out), G, *tail))
 
 
 def _sg_query_args(sgs, dirs):

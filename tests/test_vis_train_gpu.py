@@ -234,6 +234,27 @@ def test_determinism_and_partition_independence(dev, synth_weights):
     assert_parity("kernel/perturbed/M4144_default", default, t32, ref64)
 
 
+def test_more_partitions_than_one_launch_holds(dev, synth_weights):
+    """One slab of 4100 one-row partitions: more than the 4096 that one weight-gradient launch takes (Z_GROUP of csrc/train/chain.h), so
+    every layer's weight gradient is two launches, 4096 + 4 partitions, the second with part0 = 4096.  Launches: 1 encode + 4 forward +
+    5 x (2 weight-gradient + 1 reduce) + 4 data-gradient + 5 finish = 29; at part_rows = 80 (52 partitions, one launch each) 24.  The
+    partials are 4100 x 256 x 257 doubles: 2.2 GB of scratch."""
+    params = vto.vis_params(_weights(synth_weights, "perturbed"))
+    pts, dirs, g = _inputs(4100, 4, seed=4100)
+    ref64, t32 = _truth(("perturbed", 4100), params, pts, dirs, 4, g)
+    kw = dict(slab_rows=4100, part_rows=1)
+    full, stats = _kernel(dev, params, pts, dirs, 4, g, **kw)
+    assert stats["partitions"] == 4100 and stats["launches"] == 29 and stats["lowest_layer"] == 0
+    assert _kernel(dev, params, pts, dirs, 4, g, slab_rows=4100, part_rows=80)[1]["launches"] == 24
+    assert set(full) == set(vto.NAMES)
+    assert_parity("kernel/perturbed/M4100_slab4100_part1", full, t32, ref64)
+    last = ("vis_layer.8.weight", "vis_layer.8.bias")
+    sub, ss = _kernel(dev, params, pts, dirs, 4, g, want=last, **kw)
+    assert set(sub) == set(last) and ss["lowest_layer"] == 4 and ss["partitions"] == 4100
+    for k in last:
+        assert torch.equal(sub[k], full[k]), k
+
+
 # ------------------------------------------------------------------------------------------------ 6. trace_radiance
 @pytest.fixture(scope="module")
 def model(dev):
