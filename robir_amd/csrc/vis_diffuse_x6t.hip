@@ -37,6 +37,12 @@ constexpr int XT_PIECES = 6;             // 4 KB rows (1 KB per wave) of one chu
 #ifndef XT_FP8
 #define XT_FP8 1
 #endif
+template <int N>
+struct XtInt {
+  static constexpr int value = N;
+};
+// the stage instances of a chunk's epilogue (ep_slot below) that belong to tile 0
+__host__ __device__ constexpr bool xt_slot_tile0(int s) { return s == 0 || s == 1 || (s >= 4 && s <= 7); }
 
 __device__ __forceinline__ void xt_dma16(const f4* gbase_uniform, unsigned lane_byte_off, unsigned lds_byte_uniform) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_byte_uniform), "v"(lane_byte_off),
@@ -349,15 +355,18 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #else
 #define XT_T(i)
 #endif
-  for (; rd < rd_end; rd += rd_step) {
-    if constexpr (STREAM) tile_lookup(rd + rd_step);
-#ifdef XT_TIMING
-    ++trounds;
-#endif
-    XT_T(3)
+  {
+    // A round with NT live tiles per wave.  NT = 1 (per-point form): the last round of a point when it holds at most 64 samples,
+    // so that tile 1 of all four waves is padding -- tile 0's instructions are those of the two-tile round (same MFMAs in the same order
+    // on the same accumulators, same epilogue stages: bit-identical per pair), tile 1's are left out; the copies, the fragment refills
+    // and the barriers stay at full count, so the ring ends the round where a two-tile round leaves it.  It runs behind the loop of the
+    // two-tile rounds, not as a branch inside it: nothing of it is carried into another round, so tile 1's registers are dead in it
+    // (as a branch of the loop body it spilled 250 registers).
+    auto round_body = [&](auto ntc) __attribute__((always_inline)) {
+    constexpr int NT = decltype(ntc)::value;
     // ---- layer 0: relu(A[point] + Bd[dir]) straight into the operand registers
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < NT; ++t) {
       jj[t] = jjn[t];
       const f4* arow = STREAM ? a_rows + (parity * 8 + wave * 2 + t) * 64 : a_row;
 #pragma unroll
@@ -385,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
       }
     }
     XT_T(0)
-    auto layer = [&](int l, Ops& X, Ops& Y) {
+    auto layer = [&](int l, Ops& X, Ops& Y) __attribute__((always_inline)) {
       const f4* Wl = W49 + (long)l * 16 * XT_CF4 + 4;                          // this layer's chunk 0 weights
       const f4* Wn = W49 + (long)(l == 2 ? 0 : l + 1) * 16 * XT_CF4 + 4;        // next layer's (next round wraps to 0)
 #pragma unroll
@@ -452,10 +461,43 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           // the next half's fragments: second half of this chunk's slot | first half of the next chunk's
           const lds_u4p nfrag = (((jb + H) & 2) ? ring_u2 : ring_u) + ((jb + H) & 1) * XT_WF4;
           if (H == 0) {
-            acc[0].c0 = bias;
-            acc[1].c0 = bias;
-            acc[0].c1 = acc[0].c2 = acc[1].c1 = acc[1].c2 = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              acc[t].c0 = bias;
+              acc[t].c1 = acc[t].c2 = f4{0.f, 0.f, 0.f, 0.f};
+            }
           }
+#if XT_FP8
+          if constexpr (NT == 1) {
+            // tile 0's six positions (1, 2, 3, 7, 8, 11 of the two-tile body); the fragments' last use is here, so the refills follow
+            // them; a first half carries tile 0's six epilogue stages, the copies go one behind each position
+            XT_RUN(acc[0].c0, wh, X.h[0]);                       // 1
+            if (H == 0) XT_EP(0); else XT_COPY(0);
+            XT_FENCE;
+            XT_RUN_REFILL(acc[0].c1, wh, X.m[0], 0);             // 2
+            if (H == 0) XT_EP(1); else XT_COPY(1);
+            XT_FENCE;
+            XT_MFMA8(acc[0].c2, w8h, X.l8[0][H]);                // 3
+#ifndef XT_ABL_NOLDS
+            XT_LOAD8(w8h, nfrag, (1 - H) * 768 + 512)
+#endif
+            if (H == 0) XT_EP(4); else XT_COPY(2);
+            XT_FENCE;
+            XT_RUN(acc[0].c1, wm, X.h[0]);                       // 7
+            if (H == 0) XT_EP(5); else XT_COPY(3);
+            XT_FENCE;
+            XT_RUN_REFILL(acc[0].c2, wm, X.m[0], 1);             // 8
+            if (H == 0) XT_EP(6); else XT_COPY(4);
+            XT_FENCE;
+            XT_MFMA8(acc[0].c2, w8l, X.h8[0][H]);                // 11
+#ifndef XT_ABL_NOLDS
+            XT_LOAD8(w8l, nfrag, (1 - H) * 768 + 640)
+#endif
+            if (H == 0) XT_EP(7); else XT_COPY(5);
+            XT_FENCE;
+          } else
+#endif
+          {
           XT_RUN(acc[0].c0, wh, X.h[0]);                       // 1
           if (H == 0) XT_EP(0); else XT_EP(9);
           XT_FENCE;
@@ -520,6 +562,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           XT_RUN_REFILL(acc[1].c2, wl, X.h[1], 2);             // 12: the l fragments' last use
           XT_FENCE;
 #endif
+          }
         }
 #undef XT_RUN
 #undef XT_RUN_REFILL
@@ -528,12 +571,13 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #undef XT_FRAG
 #undef XT_MFMA8
 #undef XT_EP
-        prev[0] = acc[0];
-        prev[1] = acc[1];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) prev[t] = acc[t];
         bias = nbias;
       }
 #pragma unroll
-      for (int s = 0; s < 12; ++s) ep_slot(Y, s, 15);
+      for (int s = 0; s < 12; ++s)
+        if (NT == 2 || xt_slot_tile0(s)) ep_slot(Y, s, 15);
     };
     // the next layer's operands move into P at a layer's end (three copies of the layer body with alternating sets spilled, with twice
     // the code, and were removed: DESIGN section 5.3)
@@ -541,7 +585,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     for (int l = 0; l < 3; ++l) {
       layer(l, P, Q);
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int kb = 0; kb < 8; ++kb) {
           P.h[t][kb] = Q.h[t][kb];
@@ -552,7 +596,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         }
 #if XT_FP8
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
           P.h8[t][hf] = Q.h8[t][hf];
@@ -565,12 +609,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     // the head's MFMAs (clamped to this round's samples after the final round: harmless)
     XT_T(1)
     if constexpr (STREAM) fetch_rows(rd + rd_step, parity ^ 1);
-    else fetch_rows(rd + 1 < rd_end ? rd + 1 : rd, 0);
+    else if constexpr (NT == 2) fetch_rows(rd + 1 < rd_end ? rd + 1 : rd, 0);      // (a one-tile round is a point's last: nothing to fetch)
     {
       const u4* hw = reinterpret_cast<const u4*>(headw) + lane;
       SxAcc acc[2];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+      for (int t = 0; t < NT; ++t) {
         acc[t].c0 = bias;
         acc[t].c1 = f4{0.f, 0.f, 0.f, 0.f};
         acc[t].c2 = f4{0.f, 0.f, 0.f, 0.f};
@@ -580,7 +624,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
       for (int kb = 0; kb < 8; ++kb) {
         const u4 fh = hw[XT_F16OFF(kb, 0)], fm = hw[XT_F16OFF(kb, 1)];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < NT; ++t) {
           XT_MFMA(acc[t].c0, fh, P.h[t][kb]);
           XT_MFMA(acc[t].c1, fh, P.m[t][kb]);
           XT_MFMA(acc[t].c1, fm, P.h[t][kb]);
@@ -593,7 +637,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         XT_LOAD8(f8h, hw, hf * 768 + 512)
         XT_LOAD8(f8l, hw, hf * 768 + 640)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < NT; ++t) {
           acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8h, P.l8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
           acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8l, P.h8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
         }
@@ -602,7 +646,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
       for (int kb = 0; kb < 8; ++kb) {
         const u4 fh = hw[(kb * 3 + 0) * 64], fm = hw[(kb * 3 + 1) * 64], fl = hw[(kb * 3 + 2) * 64];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < NT; ++t) {
           XT_MFMA(acc[t].c0, fh, P.h[t][kb]);
           XT_MFMA(acc[t].c1, fh, P.m[t][kb]);
           XT_MFMA(acc[t].c2, fh, P.l[t][kb]);
@@ -614,7 +658,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #endif
       bias = bias_tab[g];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+      for (int t = 0; t < NT; ++t) {
         const float l0 = __builtin_fmaf(__builtin_fmaf(acc[t].c2[0], C11, acc[t].c1[0]), C11, acc[t].c0[0]);
         const float l1 = __builtin_fmaf(__builtin_fmaf(acc[t].c2[1], C11, acc[t].c1[1]), C11, acc[t].c0[1]);
         if (g == 0 && jj[t] >= 0) {
@@ -631,8 +675,30 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         }
       }
     }
-    parity ^= 1;
-    XT_T(2)
+    };
+    // the stream form's rounds stay two-tile: only the last round of a launch could be one-tile there
+    const bool tail1 = !STREAM && XT_FP8 && rounds > 0 && S - (rounds - 1) * 128 <= 64;     // workgroup-uniform
+    const long rd_end2 = tail1 ? rd_end - 1 : rd_end;
+    for (; rd < rd_end2; rd += rd_step) {
+      if constexpr (STREAM) tile_lookup(rd + rd_step);
+#ifdef XT_TIMING
+      ++trounds;
+#endif
+      XT_T(3)
+      round_body(XtInt<2>{});
+      parity ^= 1;
+      XT_T(2)
+    }
+    if constexpr (!STREAM && XT_FP8) {
+      if (tail1) {
+#ifdef XT_TIMING
+        ++trounds;
+#endif
+        XT_T(3)
+        round_body(XtInt<1>{});
+        XT_T(2)
+      }
+    }
   }
 #ifdef XT_TIMING
   if ((blockIdx.x == 7 || blockIdx.x == 4000) && tid == 0 && trounds > 0)
