@@ -5,6 +5,8 @@
 // its two halves) with the softplus epilogue of sdf_x6.hip; the skip layer's input part [x0 | 0] / sqrt 2 is rebuilt at that layer from
 // the encoder's LDS rows and the label (operands + next operands already take 408 of the 512 registers: nothing else stays resident).
 // Replaces k_softplus512 (f32-input MFMA: 41 % of BASELINE config 5 at the default precision).  Weights: packing.pack_softplus512_x6.
+// This file keeps its own ring state, unit loop and small helpers (zero_acc, combine, rotation, prologue) instead of x6_ring.h's: with the
+// shared ones the same code allocates differently (AGPR 225 -> 241 / scratch 304 -> 344 bytes: profiles/x6_engine_refactor.md).
 // The products h.xl and l.xh of the K = 256 layers as bf8 MFMAs (as in vis_diffuse_x6t.hip) measured slower, with 267 / 321 spilled
 // registers, and were removed (profiles/r06_fp8_c2.md).
 #include "../../include/robir_hip.h"
@@ -272,8 +274,6 @@ __global__ __launch_bounds__(256, 1) void k_cesr_x6(const float* __restrict__ X,
       const int c = u / HV, hvi = u % HV;
       SxAcc& acc = accs[c & 1];
       if (u > 0 && hvi == 0) zero_acc(acc, bnext);
-      constexpr int dummy2 = 0;
-      (void)dummy2;
       const int L3 = u + 3 < NU ? LI : Net::layer_of(UB + u + 3);
       const int K3 = Net::kunit(L3);
       const long in_layer = (long)((u + 3) / HV) * Net::chunk_f4s(LI) + (long)((u + 3) % HV) * (KU / 32) * 192;

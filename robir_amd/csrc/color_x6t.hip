@@ -9,24 +9,16 @@
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
-#include "x6_ring.h"
+#include "x6_layout.h"
 #include "x6t_engine.h"
 #include <type_traits>
 
 namespace rb {
 
 constexpr int CT_SLOT_B = 30 * 1024 + 512;
-constexpr int CT_NCHUNK = 65;
-__host__ __device__ constexpr int ct_K(int l) { return l == 0 ? 320 : 256; }
-__host__ __device__ constexpr int ct_nch(int l) { return l == 4 ? 1 : 16; }
-__host__ __device__ constexpr int ct_layer_of(int c) {      // stream position (cyclic: 65 chunks) -> layer
-  if (c >= CT_NCHUNK) c -= CT_NCHUNK;
-  return c >> 4;
-}
-__host__ __device__ constexpr long ct_coff(int c) {
-  if (c >= CT_NCHUNK) c -= CT_NCHUNK;
-  return c < 16 ? (long)c * sx_cf4(320) : 16 * sx_cf4(320) + (long)(c - 16) * sx_cf4(256);
-}
+using CtNet = SxColorNet;             // x6_layout.h: the blob and the stream of color_x6.hip
+using CtStream = SxStream<CtNet>;
+constexpr int CT_NCHUNK = CtStream::nchunk();
 typedef float ct_f4u __attribute__((ext_vector_type(4), aligned(4)));
 
 __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ feat, long feat_stride, float feat_scale,
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   long round = 0;
   __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(rgb, 0, 0, 0x00020000);
 
-  for (int i = tid; i < CT_NCHUNK * 4; i += 256) bias_tab[i] = Wp[ct_coff(i >> 2) + (i & 3)];
+  for (int i = tid; i < CT_NCHUNK * 4; i += 256) bias_tab[i] = Wp[CtStream::coff(i >> 2) + (i & 3)];
 
   // NONNEG: relu outputs (>= 0: the raw pattern of the h piece orders like the value, one instruction: mlp_engine.h)
   unsigned sat_in = 0u;                // ... of a round's signed inputs (sat_acc's domain): folded into `sat` at the end of the input stage
@@ -142,16 +134,16 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
 
   auto run_layer = [&](auto LI_tag, int cb) {
     constexpr int LI = decltype(LI_tag)::value;
-    constexpr int K = ct_K(LI), NCH = ct_nch(LI), CB = 16 * LI;
+    constexpr int K = CtNet::K(LI), NCH = CtNet::nch(LI), CB = 16 * LI;
     constexpr int WK = xt_wk(K), NPART = xt_parts(K), NFREE = 9 * NPART;
     constexpr bool OUT = LI == 4;
-    constexpr int WKN = xt_wk(ct_K(LI == 4 ? 0 : LI + 1));
+    constexpr int WKN = xt_wk(CtNet::K(LI == 4 ? 0 : LI + 1));
     static_assert((NCH * NPART) % 2 == 0, "a layer has an even number of parts");
     SxAcc acc[2], prev[2];
-    const f4* wl = Wp + ct_coff(cb);
+    const f4* wl = Wp + CtStream::coff(cb);
     const f4* wnext[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) wnext[i] = Wp + ct_coff(cb + NCH + i);
+    for (int i = 0; i < 3; ++i) wnext[i] = Wp + CtStream::coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
     auto bias_of = [&](int c) {
       const int cc = c >= CT_NCHUNK ? c - CT_NCHUNK : c;
@@ -181,14 +173,14 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
       // chunk jb-1, whose slot the copies of chunk jb+3 reuse
       constexpr int dummy = 0;
       (void)dummy;
-      const int K2 = jb + 2 < NCH ? K : ct_K(ct_layer_of(CB + jb + 2));
+      const int K2 = jb + 2 < NCH ? K : CtNet::K(CtStream::layer_of(CB + jb + 2));
       if (sx_nsw(K2) >= 8) sx_wait<8>();
       else sx_wait<6>();
 #ifndef CT_ABL_NOBAR                   // timing ablations (wrong results): no per-chunk barrier | no epilogue | no copies | no fragment reads
       __builtin_amdgcn_s_barrier();
 #endif
       asm volatile("" ::: "memory");
-      const int K3 = jb + 3 < NCH ? K : ct_K(ct_layer_of(CB + jb + 3));
+      const int K3 = jb + 3 < NCH ? K : CtNet::K(CtStream::layer_of(CB + jb + 3));
       const int NC3 = sx_nsw(K3);
       const int f3 = span_first(K3);
       const f4* src3 = (jb + 3 < NCH ? wl + (long)(jb + 3) * sx_cf4(K) : wnext[jb + 3 - NCH < 3 ? jb + 3 - NCH : 0]) + 4 + f3 * 64;
@@ -281,7 +273,7 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      xt_copy_piece(i, Wp + ct_coff(c) + 4 + first320 * 64, ring_b + slot_b[c] + (unsigned)first320 * 1024u);
+      xt_copy_piece(i, Wp + CtStream::coff(c) + 4 + first320 * 64, ring_b + slot_b[c] + (unsigned)first320 * 1024u);
   sx_wait<0>();
   __syncthreads();
   xt_request(win.h, ring_lane + slot_b[0], 0, 2, 0, true);

@@ -16,21 +16,16 @@
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
-#include "x6_ring.h"
+#include "x6_layout.h"
 #include "x6t_engine.h"
 #include <type_traits>
 
 namespace rb {
 
 constexpr int BT_SLOT_B = 24 * 1024;
-constexpr int BT_NCHUNK = 117;
-__host__ __device__ constexpr int bt_nch(int l) { return l == 3 ? 17 : (l == 7 ? 4 : 16); }
-__host__ __device__ constexpr int bt_cbase(int l) {
-  int n = 0;
-  for (int i = 0; i < l; ++i) n += bt_nch(i);
-  return n;
-}
-__host__ __device__ constexpr long bt_coff(int c) { return (long)(c >= BT_NCHUNK ? c - BT_NCHUNK : c) * sx_cf4(256); }
+using BtNet = SxSdfBackNet<256>;      // x6_layout.h: the stream of sdf_back_x6.hip with every layer at K = 256
+using BtStream = SxStream<BtNet>;
+constexpr int BT_NCHUNK = BtStream::nchunk();
 
 __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ sig, long M, const f4* __restrict__ Wt,
                                                           const float* __restrict__ w8row, float* __restrict__ gfeat,
@@ -107,10 +102,10 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
   // gate: sigmoid layer that gates this stream layer's outputs (stream layers 0..6: 6 - l); gate_next: ... the next stream layer's
   auto run_layer = [&](auto LI_tag, int cb, int gate, int gate_next) {
     constexpr int LI = decltype(LI_tag)::value;      // 0: hidden (stream layers 0, 1, 2, 4, 5, 6), 3: W4^T (gate + skip rows), 7: W0^T (outputs)
-    constexpr int K = 256, NCH = bt_nch(LI), WK = 4, NPART = 2, NFREE = 18;
+    constexpr int K = 256, NCH = BtNet::nch(LI), WK = 4, NPART = 2, NFREE = 18;
     constexpr bool OUT = LI == 7, SKIPL = LI == 3;
     SxAcc acc[2], prev[2];
-    const f4* wl = Wt + bt_coff(cb);
+    const f4* wl = Wt + BtStream::coff(cb);
     asm volatile("" : "+s"(wl));
     auto combine = [&](const SxAcc& a, int r) { return __builtin_fmaf(__builtin_fmaf(a.c2[r], C11, a.c1[r]), C11, a.c0[r]); };
     float z[2][4];
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int i = 0; i < 6; ++i)
-      xt_copy_piece(i, Wt + bt_coff(c) + 4 + first * 64, ring_b + slot_b[c] + (unsigned)first * 1024u);
+      xt_copy_piece(i, Wt + BtStream::coff(c) + 4 + first * 64, ring_b + slot_b[c] + (unsigned)first * 1024u);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     unsigned lv0;

@@ -8,15 +8,14 @@
 // workgroups of four waves (one 16-row tile each, one wave per SIMD), the nine layers as ONE cyclic stream of 142 / 126 chunks (16
 // output neurons x K x 3 pieces: 6 / 24 / 27 KB) through a 4-slot LDS ring filled by LDS-DMA under counted waits, one s_barrier per
 // chunk in its middle, fragment reads running across the chunk boundary, the softplus + three-way split of chunk j between the MFMAs
-// of chunk j+1, the positional encoding computed in the kernel.
+// of chunk j+1, the positional encoding computed in the kernel.  The unit loop is sx_layer (x6_ring.h), the stream geometry x6_layout.h.
 // MODE 0: signed distance only -> out0[M].   MODE 1: all 257 outputs -> out0[M,257].   MODE 5: MODE 1 + sigmoid(100 z) of every hidden
 // pre-activation -> sig [tile = row / 16][layer 8][chunk 16][lane 64] float4, the layout k_sdf_back_f32 (mlp_kernels.hip) reads.
 // Weights: packing.pack_sdf_x6 (rb_pack_layer_x6, scale 2^0; K padded to 64, 256 x3, 288 = [208 | 64 | 16 zero], 256 x4).
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
-#include "x6_ring.h"
-#include "sdf_x6_layout.h"
+#include "x6_layout.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -28,6 +27,8 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
                                                     unsigned* __restrict__ range_word) {
   constexpr bool FULL = MODE != 0, STORE = MODE == 5;
   constexpr int LAST = FULL ? 17 : 1;
+  using Net = SxSdfNet<LAST>;
+  using Stream = SxStream<Net>;
   __shared__ f4 ring[4 * SX_SLOT_B / 16];              // 110 KB
   __shared__ f4 bias_ring[4 * 16];
   __shared__ float pe_scratch[4 * 16 * 64];            // 16 KB
@@ -37,12 +38,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
   if ((long)blockIdx.x >= nrounds) return;
 
   const float negk = -2048.0f, inv_sqrt2 = 0.70710678118654752440f;
-  constexpr float C11 = 1.0f / 2048.0f;
-  const unsigned ring_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)ring);
-  const unsigned bias_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)bias_ring);
-  const unsigned lane16 = (unsigned)lane * 16u, lane4 = (unsigned)lane * 4u;
-  unsigned slot_b[4] = {0u, (unsigned)SX_SLOT_B, 2u * SX_SLOT_B, 3u * SX_SLOT_B};
-  unsigned bslot_b[4] = {0u, 256u, 512u, 768u};
+  SxRing rg = sx_ring<SX_SLOT_B>(ring, bias_ring, lane, wave);
   unsigned sat = 0u;
   u4 xh[9], xm[9], xl[9];              // operands of the current layer (K <= 288): three pieces, one tile
   u4 yh[8], ym[8], yl[8];              // ... of the next layer
@@ -95,27 +91,15 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
 
   auto run_layer = [&](auto LI_tag, int cb, int lrt) {
     constexpr int LI = decltype(LI_tag)::value;
-    constexpr int K = sx_K(LI), KB = K / 32, NCH = sx_nch(LI, LAST), NP = sx_np(K), CB = sx_cbase(LI, LAST);
+    constexpr int K = Net::K(LI), KB = K / 32, NCH = Net::nch(LI), NP = sx_np(K), CB = Stream::cbase(LI);
     constexpr bool OUT = LI == 8, SKIPOUT = LI == 3;
-    constexpr int BS = KB >= 8 ? 2 : 1, DB = 1, D = BS * DB, NB = BS * (DB + 1);     // six MFMAs per k-block: two k-blocks ahead cover the LDS latency
-    constexpr int HB = KB / 2, NSTEP = NCH * KB;
-    static_assert(D + BS - 1 <= KB - HB, "reads of the next chunk start after the barrier");
+    constexpr int BS = KB >= 8 ? 2 : 1;      // six MFMAs per k-block: two k-blocks ahead cover the LDS latency
     SxAcc accs[2];
-    f4 bnext = f4{0.f, 0.f, 0.f, 0.f};
-    u4 wfh[NB], wfm[NB], wfl[NB];
-    const f4* wl = Wp + sx_coff(cb, LAST);
+    const f4* wl = Wp + Stream::coff(cb);
     const f4* wnext[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) wnext[i] = Wp + sx_coff(cb + NCH + i, LAST);
+    for (int i = 0; i < 3; ++i) wnext[i] = Wp + Stream::coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
-    auto frag_of = [&](int c) { return reinterpret_cast<const u4*>(reinterpret_cast<const char*>(ring) + slot_b[c & 3]) + lane; };
-    auto bias_of = [&](int c) { return *(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(bias_ring) + bslot_b[c & 3]) + g); };
-    auto zero_acc = [&](SxAcc& a, const f4& b) {
-      a.c0 = b;
-      a.c1 = f4{0.f, 0.f, 0.f, 0.f};
-      a.c2 = f4{0.f, 0.f, 0.f, 0.f};
-    };
-    auto combine = [&](const SxAcc& a, int r) { return __builtin_fmaf(__builtin_fmaf(a.c2[r], C11, a.c1[r]), C11, a.c0[r]); };
     // hidden chunk pj: softplus (+ its sigmoid in MODE 5), three-way split into the next layer's operand registers
     // hidden chunk pj in four stages (they go between the MFMA runs of the next chunk, one per run): A = softplus (+ its sigmoid in
     // MODE 5) of a value pair, B = exact three-way split into the next layer's operand registers
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
     auto stage_a = [&](const SxAcc& a, int q, f4& sg) {
       float s0, s1;
       // the overflow-free form (mlp_engine.h: max(z, 0) + a correction <= 0.0069 from the hardware exp2 / log2)
-      float v0 = softplus100_stable(combine(a, 2 * q), &s0), v1 = softplus100_stable(combine(a, 2 * q + 1), &s1);
+      float v0 = softplus100_stable(sx_combine(a, 2 * q), &s0), v1 = softplus100_stable(sx_combine(a, 2 * q + 1), &s1);
       if (SKIPOUT) {
         v0 *= inv_sqrt2;
         v1 *= inv_sqrt2;
@@ -144,158 +128,64 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
       for (int r = 0; r < 4; ++r) {
         const int j = pj * 16 + 4 * g + r;
         if constexpr (FULL) {
-          if (j < 257) out0[rrow * 257 + j] = combine(a, r) * out_scale;
+          if (j < 257) out0[rrow * 257 + j] = sx_combine(a, r) * out_scale;
         } else {
-          if (j == 0) out0[rrow] = combine(a, r) * out_scale;
+          if (j == 0) out0[rrow] = sx_combine(a, r) * out_scale;
         }
       }
     };
-    zero_acc(accs[0], bias_of(0));
-#pragma unroll
-#ifdef SXA_NOREAD
-    for (int i = 0; i < NB; ++i)
-#else
-    for (int i = 0; i < D; ++i)
-#endif
-      if (i < NSTEP) {
-        const u4* f = frag_of(i / KB) + (3 * (i % KB)) * 64;
-        wfh[i % NB] = f[0];
-        wfm[i % NB] = f[64];
-        wfl[i % NB] = f[128];
-      }
     f4 sgp = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int jb = 0; jb < NCH; ++jb) {
-      SxAcc& acc = accs[jb & 1];
-      if (jb > 0) zero_acc(acc, bnext);
-      constexpr int dummy2 = 0;
-      (void)dummy2;
-      const int K3 = jb + 3 < NCH ? K : sx_K(sx_layer_of(CB + jb + 3, LAST));
-      const int nu3 = sx_units(K3);
-      const f4* src3 = jb + 3 < NCH ? wl + (long)(jb + 3) * sx_cf4(K) : wnext[jb + 3 - NCH < 3 ? jb + 3 - NCH : 0];
-      const int sl3 = (jb + 3) & 3;
-      const unsigned dst3 = ring_b + slot_b[sl3], bdst3 = bias_b + bslot_b[sl3];
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) {
-        const int st = jb * KB + kb;
-        if (kb == HB) {   // chunk jb+1 must have landed: this wave's copies of chunk jb+2 may still be in flight
-          const int allowed = jb + 2 < NCH ? NP : sx_np(sx_K(sx_layer_of(CB + jb + 2, LAST)));
+    sx_layer<KB, NCH, BS, 1, SxKs<64, 256, 288>>(
+        rg, accs, xh, xm, xl,
+        [&](int jb) {      // chunk jb+1 must have landed: this wave's copies of chunk jb+2 may still be in flight
+          const int allowed = jb + 2 < NCH ? NP : sx_np(Net::K(Stream::layer_of(CB + jb + 2)));
           if (allowed >= 8) sx_wait<8>();
           else if (allowed >= 7) sx_wait<7>();
           else sx_wait<3>();
-#ifndef SXA_NOBAR
-          __builtin_amdgcn_s_barrier();
-#endif
-          asm volatile("" ::: "memory");
-          bnext = bias_of(jb + 1);
-        }
-#ifdef SXA_NOREAD                     // no fragment reads: the registers are redefined behind the compiler's back (no instruction)
-        if (st % BS == 0) {
-#pragma unroll
-          for (int i = BS - 1; i >= 0; --i) {
-            const int s2 = st + D + i;
-            if (s2 < NSTEP) asm volatile("" : "+v"(wfl[s2 % NB]), "+v"(wfm[s2 % NB]), "+v"(wfh[s2 % NB]));
-          }
-        }
-#else
-        if (st % BS == 0) {
-#pragma unroll
-          for (int i = BS - 1; i >= 0; --i) {
-            const int s2 = st + D + i;
-            if (s2 < NSTEP) {
-              const u4* f = frag_of(s2 / KB) + (3 * (s2 % KB)) * 64;
-              wfl[s2 % NB] = f[128];
-              wfm[s2 % NB] = f[64];
-              wfh[s2 % NB] = f[0];
-            }
-          }
-        }
-#endif
-        // the six products of BS k-blocks, a run per accumulator: class 2 (wl.xh, wm.xm, wh.xl), class 1 (wm.xh, wh.xm), class 0 (wh.xh)
-        if (st % BS == BS - 1 || kb == KB - 1) {
-          const int k0 = (st % BS == BS - 1) ? (kb - (BS - 1) > 0 ? kb - (BS - 1) : 0) : kb - (st % BS);
-#define SX_MFMA(ACC, W, X) ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, W), __builtin_bit_cast(h8, X), ACC, 0, 0, 0)
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c2, wfl[(jb * KB + k) % NB], xh[k]);
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c2, wfm[(jb * KB + k) % NB], xm[k]);
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c2, wfh[(jb * KB + k) % NB], xl[k]);
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c1, wfm[(jb * KB + k) % NB], xh[k]);
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c1, wfh[(jb * KB + k) % NB], xm[k]);
-#pragma unroll
-          for (int k = k0; k <= kb; ++k) SX_MFMA(acc.c0, wfh[(jb * KB + k) % NB], xh[k]);
-#undef SX_MFMA
-        }
-#ifdef SXA_NOEPI                      // timing ablations (wrong results): -DSXA_NOEPI / _NOREAD / _NODMA / _NOBAR
-        if (jb > 0 && kb == KB - 1) {         // the data dependence of the epilogue without its arithmetic
-          const SxAcc& pa = accs[(jb - 1) & 1];
-          const int pj = jb - 1;
-          if (OUT) output_chunk(pa, pj);
-          else
-            for (int q = 0; q < 2; ++q) {
-              const unsigned hv = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(pa.c0[2 * q] + pa.c1[2 * q], pa.c0[2 * q + 1] + pa.c2[2 * q + 1]));
-              yh[pj >> 1][(pj & 1) * 2 + q] = hv;
-              ym[pj >> 1][(pj & 1) * 2 + q] = hv;
-              yl[pj >> 1][(pj & 1) * 2 + q] = hv;
-            }
-        }
-#else
-        if (jb > 0 && (st % BS == BS - 1 || kb == KB - 1)) {      // epilogue of chunk jb-1: a stage beside every MFMA run
-          constexpr int dummy3 = 0;
-          (void)dummy3;
-          int nm = 0, mi = 0;                    // MFMA-issuing k-blocks of this chunk; index of this one
-          for (int k = 0; k < KB; ++k) {
-            const bool issues = ((jb * KB + k) % BS == BS - 1) || k == KB - 1;
-            if (issues && k < kb) ++mi;
-            if (issues) ++nm;
-          }
-#pragma unroll
-          for (int sgi = 0; sgi < 4; ++sgi)
-            if ((sgi * nm) / 4 == mi) {
-              const SxAcc& pa = accs[(jb - 1) & 1];
-              if (OUT) {
-                if (sgi == 0) output_chunk(pa, jb - 1);
-              } else if (sgi == 0) stage_a(pa, 0, sgp);
-              else if (sgi == 1) stage_b(jb - 1, 0);
-              else if (sgi == 2) stage_a(pa, 1, sgp);
-              else {
-                stage_b(jb - 1, 1);
-                store_sig(jb - 1, sgp);
+        },
+        [&](int j3) {
+          return SxSrc{j3 < NCH ? wl + (long)j3 * sx_cf4(K) : wnext[j3 - NCH < 3 ? j3 - NCH : 0], j3 < NCH ? K : Net::K(Stream::layer_of(CB + j3))};
+        },
+        [&](int jb, int kb) {
+          const int st = jb * KB + kb;
+#ifdef SXA_NOEPI                      // timing ablation (wrong results): the data dependence of the epilogue without its arithmetic
+          if (jb > 0 && kb == KB - 1) {
+            const SxAcc& pa = accs[(jb - 1) & 1];
+            const int pj = jb - 1;
+            if (OUT) output_chunk(pa, pj);
+            else
+              for (int q = 0; q < 2; ++q) {
+                const unsigned hv = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(pa.c0[2 * q] + pa.c1[2 * q], pa.c0[2 * q + 1] + pa.c2[2 * q + 1]));
+                yh[pj >> 1][(pj & 1) * 2 + q] = hv;
+                ym[pj >> 1][(pj & 1) * 2 + q] = hv;
+                yl[pj >> 1][(pj & 1) * 2 + q] = hv;
               }
+          }
+#else
+          if (jb > 0 && (st % BS == BS - 1 || kb == KB - 1)) {      // epilogue of chunk jb-1: a stage beside every MFMA run
+            int nm = 0, mi = 0;                    // MFMA-issuing k-blocks of this chunk; index of this one
+            for (int k = 0; k < KB; ++k) {
+              const bool issues = ((jb * KB + k) % BS == BS - 1) || k == KB - 1;
+              if (issues && k < kb) ++mi;
+              if (issues) ++nm;
             }
-        }
+#pragma unroll
+            for (int sgi = 0; sgi < 4; ++sgi)
+              if ((sgi * nm) / 4 == mi) {
+                const SxAcc& pa = accs[(jb - 1) & 1];
+                if (OUT) {
+                  if (sgi == 0) output_chunk(pa, jb - 1);
+                } else if (sgi == 0) stage_a(pa, 0, sgp);
+                else if (sgi == 1) stage_b(jb - 1, 0);
+                else if (sgi == 2) stage_a(pa, 1, sgp);
+                else {
+                  stage_b(jb - 1, 1);
+                  store_sig(jb - 1, sgp);
+                }
+              }
+          }
 #endif
-#ifndef SXA_NODMA
-        if (kb >= HB) {
-#pragma unroll
-          for (int u = 0; u < 3; ++u)
-            if (u < nu3 && (u * (KB - HB)) / nu3 == kb - HB) {
-              if (K3 == 64) sx_copy_unit<64>(u, src3, lane4, lane16, bdst3, dst3, wave);
-              else if (K3 == 256) sx_copy_unit<256>(u, src3, lane4, lane16, bdst3, dst3, wave);
-              else sx_copy_unit<288>(u, src3, lane4, lane16, bdst3, dst3, wave);
-            }
-        }
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    {   // slot 0 = the slot of the next layer's first chunk
-      constexpr int R = NCH & 3;
-      unsigned a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        a[i] = slot_b[(i + R) & 3];
-        b[i] = bslot_b[(i + R) & 3];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        slot_b[i] = a[i];
-        bslot_b[i] = b[i];
-      }
-    }
+        });
     const SxAcc& last = accs[(NCH - 1) & 1];
     if constexpr (OUT) {
       output_chunk(last, NCH - 1);
@@ -343,14 +233,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6(const float* __restrict__ xyz
   };
 
   // ---- prologue: chunks 0, 1, 2 of the stream (layer 0: K = 64)
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      sx_copy_unit<64>(u, Wp + sx_coff(c, LAST), lane4, lane16, bias_b + bslot_b[c], ring_b + slot_b[c], wave);
-  sx_wait<0>();
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  sx_prologue<64>(rg, [&](int c) { return Wp + Stream::coff(c); });
 
   for (long round = blockIdx.x; round < nrounds; round += gridDim.x) {
     rrow = round * 64 + wave * 16 + (lane & 15);

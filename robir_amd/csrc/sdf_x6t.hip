@@ -21,7 +21,7 @@
 #include "common.h"
 #include "mlp_engine.h"
 #include "x6_ring.h"
-#include "sdf_x6_layout.h"
+#include "x6_layout.h"
 #include "x6t_engine.h"
 #include <type_traits>
 
@@ -32,7 +32,10 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
                                                      float out_scale, float* __restrict__ out0, f4* __restrict__ sig,
                                                      unsigned* __restrict__ range_word) {
   constexpr bool FULL = MODE != 0, STORE = MODE == 5;
-  constexpr int LAST = FULL ? 17 : 1, NCHUNK = sx_nchunk(LAST);
+  constexpr int LAST = FULL ? 17 : 1;
+  using Net = SxSdfNet<LAST>;
+  using Stream = SxStream<Net>;
+  constexpr int NCHUNK = Stream::nchunk();
   __shared__ f4 ring[4 * SX_SLOT_B / 16];              // 110 KB
   __shared__ f4 bias_tab[NCHUNK * 4];                  // 9 KB: the 16 biases of every chunk of the stream
   __shared__ float pe_scratch[4 * 2 * 16 * 64];        // 32 KB: [wave][tile][row 16][64 encoded inputs]
@@ -65,7 +68,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   long round = 0;
   auto row_of = [&](int t) { return round * 128 + t * 64 + rlocal; };
 
-  for (int i = tid; i < NCHUNK * 4; i += 256) bias_tab[i] = Wp[sx_coff(i >> 2, LAST) + (i & 3)];
+  for (int i = tid; i < NCHUNK * 4; i += 256) bias_tab[i] = Wp[Stream::coff(i >> 2) + (i & 3)];
 
   // range sentinel: `sat` in the domain of sat_acc_nonneg (softplus outputs are >= 0: the raw pattern of the h piece orders like the value,
   // one instruction per pair); the signed inputs of a round (encoded rows) go through sat_acc into `sat_in`, folded into `sat` behind them
@@ -123,12 +126,12 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
 
   auto run_layer = [&](auto LI_tag, int cb, int lrt) {
     constexpr int LI = decltype(LI_tag)::value;
-    constexpr int K = sx_K(LI), NCH = sx_nch(LI, LAST), CB = sx_cbase(LI, LAST);
+    constexpr int K = Net::K(LI), NCH = Net::nch(LI), CB = Stream::cbase(LI);
     constexpr int WK = xt_wk(K), NPART = xt_parts(K), NFREE = 9 * NPART;
     constexpr bool OUT = LI == 8, SKIPOUT = LI == 3;
-    constexpr int KN = sx_K(LI == 8 ? 0 : LI + 1), WKN = xt_wk(KN);
+    constexpr int KN = Net::K(LI == 8 ? 0 : LI + 1), WKN = xt_wk(KN);
     static_assert((NCH * NPART) % 2 == 0, "a layer has an even number of parts");
-    constexpr int PNCH = sx_nch(LI == 0 ? 8 : LI - 1, LAST);      // chunks of the layer that runs before this one (layer 8 of the previous round)
+    constexpr int PNCH = Net::nch(LI == 0 ? 8 : LI - 1);      // chunks of the layer that runs before this one (layer 8 of the previous round)
     // stores of the epilogue of chunk pj (pj < 0: no such chunk) of an output / a hidden layer
     auto ep_stores = [](bool out_layer, int pj) {
       if (pj < 0) return 0;
@@ -137,10 +140,10 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
     };
     SxAcc acc[2];
     constexpr bool PREV_SKIPOUT = LI == 4, PEND = LI != 0;      // the layer before this one: its outputs are scaled (layer 3) / it left its last chunk pending (every hidden layer)
-    const f4* wl = Wp + sx_coff(cb, LAST);
+    const f4* wl = Wp + Stream::coff(cb);
     const f4* wnext[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) wnext[i] = Wp + sx_coff(cb + NCH + i, LAST);
+    for (int i = 0; i < 3; ++i) wnext[i] = Wp + Stream::coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
     auto bias_of = [&](int c) {      // c = stream position (may run past the end once)
       const int cc = c >= NCHUNK ? c - NCHUNK : c;
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
       // wait stricter); past the barrier every wave has finished with chunk jb-1, whose slot the copies of chunk jb+3 reuse
       constexpr int dummy = 0;
       (void)dummy;
-      const int K2 = jb + 2 < NCH ? K : sx_K(sx_layer_of(CB + jb + 2, LAST));
+      const int K2 = jb + 2 < NCH ? K : Net::K(Stream::layer_of(CB + jb + 2));
       // ... plus the stores of the epilogue items that ran beside them (exact: every store is issued, lanes out of range are dropped by
       // the descriptor): the previous chunk carried the epilogue of the chunk before it; a layer's first chunk follows the previous
       // layer's last chunk AND the tail epilogue of that chunk
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
       __builtin_amdgcn_s_barrier();
 #endif
       asm volatile("" ::: "memory");
-      const int K3 = jb + 3 < NCH ? K : sx_K(sx_layer_of(CB + jb + 3, LAST));
+      const int K3 = jb + 3 < NCH ? K : Net::K(Stream::layer_of(CB + jb + 3));
       const int NC3 = sx_nsw(K3);
       const int f3 = span_first(K3);
       const f4* src3 = (jb + 3 < NCH ? wl + (long)(jb + 3) * sx_cf4(K) : wnext[jb + 3 - NCH < 3 ? jb + 3 - NCH : 0]) + 4 + f3 * 64;
@@ -391,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      xt_copy_piece(i, Wp + sx_coff(c, LAST) + 4 + first64 * 64, ring_b + slot_b[c] + (unsigned)first64 * 1024u);
+      xt_copy_piece(i, Wp + Stream::coff(c) + 4 + first64 * 64, ring_b + slot_b[c] + (unsigned)first64 * 1024u);
   sx_wait<0>();
   __syncthreads();
   xt_request(win.h, ring_lane + slot_b[0], 0, 2, 0, true);

@@ -480,11 +480,6 @@ def pack_softplus512_h3(sd, prefix, k_in, device):
     return pack_layers_h3(ls, device)
 
 
-def repack_vis_x6_fp8(blob, device):
-    """EXPERIMENT (csrc/vis_x6.hip built with -DVX_FP8=1): the blob of pack_vis_x6 in the bf8 layout of repack_x6_chunks_fp8."""
-    return repack_x6_chunks_fp8(blob, device, ((128, 16), (256, 16), (256, 16), (256, 16), (256, 1)))
-
-
 def repack_x6_chunks_fp8(blob, device, layout):
     """A blob of exact-operand chunks (rb_pack_layer_x6: per chunk [16 bias floats][k-block][h | m | l][lane][8 halves]; `layout` = its (K,
     number of chunks) runs) with the l pieces of every weight replaced by bf8 (e5m2) copies of the h and l pieces in the K = 128 order of

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Timing of the exact-operand CESR nets of one library build: `python tools/ab_cesr_x6.py <tag> <lib.so>` (A/B and ablation builds made
+"""Timing of the exact-operand CESR nets of one library build: `python tools/ab_cesr_x6.py [<tag> [<lib.so>]]` (the library: the argument, else ROBIR_AB_LIB, else the shipped one; A/B and ablation builds made
 by tools/build_variant.sh; -DQX_ABL_* builds give wrong results on purpose).  shadow_net: 8192 points x 128 labels = 2^20 rows."""
 import os
 import sys
@@ -8,7 +8,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-tag, lib = sys.argv[1], sys.argv[2]
+tag = sys.argv[1] if len(sys.argv) > 1 else "shipped"
+lib = sys.argv[2] if len(sys.argv) > 2 else os.environ.get("ROBIR_AB_LIB", "robir_amd/librobir_hip.so")
 from robir_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.join(ROOT, lib)
 from robir_amd import ops, packing, synth  # noqa: E402

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Timing of the exact-operand SDF kernels of one library build: `python tools/ab_sdf_x6.py <tag> <lib.so>` (A/B and ablation builds
-made by tools/build_variant.sh; -DSXA_* builds give wrong results on purpose)."""
+"""Timing of the exact-operand SDF kernels of one library build: `python tools/ab_sdf_x6.py [<tag> [<lib.so>]]` (the library: the argument, else ROBIR_AB_LIB, else the shipped one; A/B and ablation builds
+made by tools/build_variant.sh; the engine's -DSX_ABL_NOBAR / _NOREAD / _NODMA (csrc/x6_ring.h) and the SDF epilogue's -DSXA_NOEPI give
+wrong results on purpose)."""
 import os
 import sys
 
@@ -8,7 +9,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-tag, lib = sys.argv[1], sys.argv[2]
+tag = sys.argv[1] if len(sys.argv) > 1 else "shipped"
+lib = sys.argv[2] if len(sys.argv) > 2 else os.environ.get("ROBIR_AB_LIB", "robir_amd/librobir_hip.so")
 from robir_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.join(ROOT, lib)
 from robir_amd import ops, packing, synth  # noqa: E402

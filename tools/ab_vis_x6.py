@@ -1,9 +1,8 @@
 #!/usr/bin/env python
-"""EXPERIMENT: the stand-alone visibility MLP kernel k_vis_x6 with h.xl and l.xh as bf8 products on
-v_mfma_f32_16x16x128_f8f6f4 (a library built by `bash tools/build_variant.sh vfp8 vis_x6.hip -DVX_FP8=1 ...`), against the shipped
-exact-operand kernel and a float64 evaluation of the network (plain torch on the CPU, written out below).
-`python tools/ab_vis_fp8.py <lib.so> [fp8]`: time per 2^20 rows, error of the logits against float64 (median / 99th percentile / maximum of
-|a - b| / (|b| + mean|b|)) for this library's kernel and for PyTorch-CPU fp32."""
+"""Timing and accuracy of the stand-alone exact-operand visibility kernel k_vis_x6 (csrc/vis_x6.hip): `python tools/ab_vis_x6.py`, or
+`ROBIR_AB_LIB=<lib.so> python tools/ab_vis_x6.py` for an A/B or ablation build made by tools/build_variant.sh.  Time per 2^20 rows; error of
+the logits against a float64 evaluation of the network (plain torch on the CPU, written out below: median / 99th percentile / maximum
+of |a - b| / (|b| + mean|b|)) for the kernel and for PyTorch-CPU fp32."""
 import os
 import sys
 
@@ -12,9 +11,10 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-lib, fp8 = sys.argv[1], "fp8" in sys.argv[2:]
-from robir_amd import _lib  # noqa: E402
-_lib.LIB_PATH = os.path.join(ROOT, lib)
+lib = os.environ.get("ROBIR_AB_LIB", "robir_amd/librobir_hip.so")
+if os.environ.get("ROBIR_AB_LIB"):
+    from robir_amd import _lib
+    _lib.LIB_PATH = os.path.join(ROOT, lib)
 from robir_amd import ops, packing, synth  # noqa: E402
 
 
@@ -33,8 +33,6 @@ def vis_logits(sd, p, d):
 dev = torch.device("cuda:0")
 sd_np = synth.synth_state_dict(0)
 blob = packing.pack_vis_x6(sd_np, dev)
-if fp8:
-    blob = packing.repack_vis_x6_fp8(blob, dev)
 g = torch.Generator().manual_seed(5)
 n = 8192
 x = (torch.rand(n, 3, generator=g) - 0.5) * 0.8
@@ -52,7 +50,7 @@ def err(a):
     return "%.2e / %.2e / %.2e" % (float(e.median()), float(e.kthvalue(int(0.99 * e.numel())).values), float(e.max()))
 
 
-print("%s%s: kernel vs float64 %s | PyTorch-CPU fp32 vs float64 %s" % (lib, " (bf8 low-weight products)" if fp8 else "", err(got), err(o32)), flush=True)
+print("%s: kernel vs float64 %s | PyTorch-CPU fp32 vs float64 %s" % (lib, err(got), err(o32)), flush=True)
 m = 1 << 20
 xb = ((torch.rand(m, 3, generator=g) - 0.5) * 0.8).to(dev)
 vb = F.normalize(torch.randn(m, 3, generator=g), dim=-1).to(dev)

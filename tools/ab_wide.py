@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Timing of the chunk-stream colour / 512-wide kernels of one library build: `python tools/ab_wide.py <tag> <lib.so>` (A/B and
+"""Timing of the chunk-stream colour / 512-wide kernels of one library build: `python tools/ab_wide.py [<tag> [<lib.so>]]` (the library: the argument, else ROBIR_AB_LIB, else the shipped one; A/B and
 ablation builds made by tools/build_variant.sh)."""
 import os
 import sys
@@ -8,7 +8,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-tag, lib = sys.argv[1], sys.argv[2]
+tag = sys.argv[1] if len(sys.argv) > 1 else "shipped"
+lib = sys.argv[2] if len(sys.argv) > 2 else os.environ.get("ROBIR_AB_LIB", "robir_amd/librobir_hip.so")
 which = sys.argv[3] if len(sys.argv) > 3 else "color,decoder,encoder,normal,shadow"
 from robir_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.join(ROOT, lib)
