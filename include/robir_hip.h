@@ -200,7 +200,10 @@ int rb_dvis_fused(const float* normals, const int* chunk_id, long n, const float
  * mismatch is refused).  One workgroup of
  * four waves per point, TWO 16-sample tiles per wave (a weight fragment read from the LDS feeds both tiles, a pass of the weights
  * serves 128 samples), output layer on the matrix pipe.  Other arguments as rb_dvis_fused; vis_out agrees with its precision 0 to
- * fp32 summation order. */
+ * fp32 summation order.  The grid is PERSISTENT: min(n, workgroups) workgroups take point after point, in ascending order, from a queue
+ * (a library-internal device counter, zeroed on `stream` in front of the launch) and keep the weight ring running across points.
+ * `workgroups` is one per compute unit unless the environment variable ROBIR_DVIS_PT_WORKGROUPS, read at every launch, holds a
+ * positive number (tests and A/B runs; robir_amd.ops.DVIS_PT_WORKGROUPS sets it): the results do not depend on it. */
 int rb_dvis_fused_x6t(const float* normals, const int* chunk_id, long n, const float* A, const float* Bd, const float* dirs,
                       const float* wdir, const float* wsum, const float* W49, int L, int nsamp, int argmax_vis, int scale_log2,
                       float* vis_out, unsigned long long* eval_count, rb_stream_t stream);

@@ -13,10 +13,21 @@
 // Arithmetic: that of k_dvis_x6 (three-piece operands, six products, one fp32 accumulator per weight class; see its header).  The
 // products of a class are summed half-chunk by half-chunk (h.h | h.m, m.h | h.l, m.m, l.h per four k-blocks), not product by product
 // over the whole chunk: another -- equally valid -- fp32 summation order, so the results differ from k_dvis_x6's in the last bits.
+//
+// The point loop (per-point form; DESIGN section 5.6 item 12, profiles/dvis_persistent_ab.md).  The grid is min(n, one workgroup per CU).
+// A workgroup loads bias_tab and the head chunk and primes the weight ring once, then repeats: take the next point from the queue
+// (ascending) | A row, zeroed visibility table, cull + compaction | rows of the first round | the point's two-tile rounds and, for
+// at most 64 samples in the last one, the one-tile round | barrier, per-lobe reduce in the fixed sample order.  The ring is never
+// drained between points: the stream of chunk copies that a point's last layer continues into "the next round" IS the next point's
+// first round.  eval_count is summed per workgroup and added once; the range sentinel is reported once.  Outputs are bit-identical
+// to one workgroup per point (the same instructions per pair; only the order of points on a compute unit differs).
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include "x6_ring.h"
+#include <atomic>
+#include <cstdlib>
+#include <mutex>
 
 namespace rb {
 
@@ -72,12 +83,14 @@ struct XtArgs {
   const f4* W49;
   int argmax_vis;
   unsigned* range_word;
-  // one workgroup per point (STREAM = false)
+  // a persistent grid over the points (STREAM = false)
   const float *normals, *dirs, *wdir, *wsum;
   const int* cid;
   int L, nsamp;
   float* vis_out;
   unsigned long long* eval_count;
+  long n;
+  unsigned* queue;      // the next point to hand out (zeroed in front of the launch)
   // persistent grid over the global tile list (STREAM = true; k_dvis3_cull / k_dvis3_reduce of vis_diffuse_v3.hip around it)
   const unsigned short* pair_j;
   const XtTile* tile_info;
@@ -85,7 +98,16 @@ struct XtArgs {
   float* pair_vis;
 };
 
-// STREAM = false: one workgroup per surface point, rounds of 128 of its front-facing directions (cull and per-lobe means in the kernel).
+// STREAM = false: a workgroup works on one surface point at a time, in rounds of 128 of its front-facing directions (cull and per-lobe
+//   means in the kernel), and the grid is PERSISTENT: min(n, one workgroup per CU) workgroups take point
+//   after point from a queue -- one global counter, so that points are handed out in ascending order and the workgroups running at
+//   one time work on neighbouring points of one chunk (the L2 window over the direction table), balanced by
+//   demand as hardware dispatch balanced one workgroup per point.  bias_tab and headw are loaded and the ring is primed ONCE per
+//   workgroup: a point's last layer already prefetches chunks 0..2 of "the next round", the fragment window holds the first half of
+//   chunk 0 and `bias` is restored by the head, so the next point's first round finds the ring exactly where a next round of the same
+//   point would (the one-tile last round leaves it there too); a point without front-facing directions runs no round and leaves the
+//   ring untouched.  Between two points stand only the boundary's own steps (below: reduce, claim, cull, first rows); there is one
+//   drain, at the end of the workgroup.
 // STREAM = true: a persistent grid walks the global list of 16-sample tiles eight tiles per round, whatever point they belong to:
 //   every tile has its own layer-0 point row (LDS-DMA into a wave-private slot during the previous round's head); the weight ring
 //   runs continuously across rounds; per-pair visibilities go to a global array.  The same instruction sequence per pair: the two
@@ -98,6 +120,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   // per point: vis_tab[4096] float | idx_list[4096] u16 | a_row[64] f4 = 25 KB; stream: a_rows [round parity][tile of the round][64] f4 = 16 KB
   __shared__ f4 aux[(XT_MAX_DIRS * 4 + XT_MAX_DIRS * 2) / 16 + 64];
   __shared__ int s_count;
+  __shared__ unsigned s_next;              // per-point form: the point lane 0 took from the queue
   float* const vis_tab = reinterpret_cast<float*>(aux);
   unsigned short* const idx_list = reinterpret_cast<unsigned short*>(aux + XT_MAX_DIRS / 4);
   f4* const a_row = aux + (XT_MAX_DIRS * 6) / 16;
@@ -110,11 +133,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float negk = -2048.0f;
   constexpr float C11 = 1.0f / 2048.0f;
-  // per-point form
-  const long p = blockIdx.x;
+  // per-point form: the point at hand (workgroup-uniform, set at every point boundary: point_begin below)
+  long p = 0;
   const int L = a.L, nsamp = a.nsamp, LS = L * nsamp;
   long dbase = 0;
   int S = 0, rounds = 0;
+  unsigned long long evals = 0;        // surviving pairs of this workgroup's points, added to eval_count once
   // stream form
   const int G = gridDim.x;
   long total_tiles = 0, total_rounds = 0;
@@ -127,34 +151,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     if ((long)blockIdx.x >= total_rounds) return;           // workgroup-uniform
     rounds = 1;
   } else {
-  const float* __restrict__ normals = a.normals;
-  const float* __restrict__ dirs = a.dirs;
-  const int* __restrict__ cid = a.cid;
-  dbase = (cid ? (long)cid[p] : 0L) * LS;
-  if (tid == 0) s_count = 0;
-  if (tid < 64) a_row[tid] = reinterpret_cast<const f4*>(A + p * 256)[tid];
-  for (int j = tid; j < LS; j += 256) vis_tab[j] = 0.f;
-  __syncthreads();
-  // ---- cull + compaction (order inside the list is irrelevant: results are scattered by direction index)
-  const float nx = normals[3 * p], ny = normals[3 * p + 1], nz = normals[3 * p + 2];
-  for (int j0 = 0; j0 < LS; j0 += 256) {
-    const int j = j0 + tid;
-    bool front = false;
-    if (j < LS) {
-      const float* d = dirs + 3 * (dbase + j);
-      const float c = nx * d[0] + ny * d[1] + nz * d[2];  // sum(n*d): separate mul/add (-ffp-contract=off)
-      front = c > RB_TINY;
-    }
-    const unsigned long long mk = __ballot(front);
-    int base = 0;
-    if (lane == 0 && mk) base = atomicAdd(&s_count, __popcll(mk));
-    base = __shfl(base, 0);
-    if (front) idx_list[base + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)j;
-  }
-  __syncthreads();
-  S = s_count;
-  if (tid == 0 && a.eval_count) atomicAdd(a.eval_count, (unsigned long long)S);
-  rounds = (S + 127) / 128;
+    __syncthreads();                                        // the tables; the ring is primed whatever the first point holds
   }
 
   // ---- weight ring state
@@ -184,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   }
 #endif
   f4 bias;
-  if (rounds > 0) {
+  if (!STREAM || rounds > 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -343,17 +340,94 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
       for (int kb = 0; kb < 16; ++kb) raw[t][kb] = brow[kb * 4];
     }
   };
+  // ---- the boundary between two points of the per-point form: out of line of the two round loops.  point_begin takes the next
+  // point from the queue (lane 0, an ordinary atomicAdd, broadcast through the LDS), builds its tables (A row, zeroed visibility
+  // table, cull + compaction) and requests its first round's rows; point_end is the per-lobe reduce of the point just finished.
+  // Barriers: (1) behind the claim -- it also separates the previous point's reduce from the zeroing of vis_tab --, (2) behind the cull,
+  // (3) in front of the reduce.  The previous point's rounds are over for every wave at (3), so a_row, idx_list, s_count and s_next
+  // are free to be rewritten behind it.
+  // vmcnt: the ring's counted waits (vmcnt(6) per chunk) assume that the ring's copies are the only VMEM operations of the wave that
+  // are younger than the rows of the round at hand, and on this target stores count in vmcnt and may retire out of order with
+  // loads.  The boundary issues stores (vis_out) and an atomic, so every wave waits vmcnt(0) in front of barrier (2): nothing of the
+  // boundary is in flight when a round starts.  This also waits for the ring's chunks 0..2 of the coming round, which the previous
+  // point's last layer requested a whole layer ago (at the first point: the prime): they landed long before, the wait costs the
+  // latency of the boundary's own stores only; and a ring with NO copy in flight is what vmcnt(6) ("at most six") allows.  The
+  // compiler's own waits inside the boundary count only the operations it knows: with the ring's (older, in-order) copies in
+  // flight they wait for more than they need, never for less.
+  auto point_begin = [&]() -> bool {
+    int btid = tid;                                         // (opaque: nothing of the boundary is computed ahead of the point loop and
+    asm volatile("" : "+v"(btid));                          //  held in registers through the rounds)
+    const int blane = btid & 63;
+    const float* __restrict__ normals = a.normals;
+    const float* __restrict__ dirs = a.dirs;
+    const int* __restrict__ cid = a.cid;
+    if (btid == 0) {
+      s_next = atomicAdd(a.queue, 1u);
+      s_count = 0;
+    }
+    __syncthreads();
+    const long pn = (long)(unsigned)__builtin_amdgcn_readfirstlane((int)s_next);
+    if (pn >= a.n) return false;                            // workgroup-uniform: the queue is empty
+    p = pn;
+    dbase = (cid ? (long)cid[p] : 0L) * LS;
+    if (btid < 64) a_row[btid] = reinterpret_cast<const f4*>(A + p * 256)[btid];
+    for (int j = btid; j < LS; j += 256) vis_tab[j] = 0.f;
+    // ---- cull + compaction (order inside the list is irrelevant: results are scattered by direction index)
+    const float nx = normals[3 * p], ny = normals[3 * p + 1], nz = normals[3 * p + 2];
+    for (int j0 = 0; j0 < LS; j0 += 256) {
+      const int j = j0 + btid;
+      bool front = false;
+      if (j < LS) {
+        const float* d = dirs + 3 * (dbase + j);
+        const float c = nx * d[0] + ny * d[1] + nz * d[2];  // sum(n*d): separate mul/add (-ffp-contract=off)
+        front = c > RB_TINY;
+      }
+      const unsigned long long mk = __ballot(front);
+      int base = 0;
+      if (blane == 0 && mk) base = atomicAdd(&s_count, __popcll(mk));
+      base = __shfl(base, 0);
+      if (front) idx_list[base + __popcll(mk & ((1ull << blane) - 1ull))] = (unsigned short)j;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    S = __builtin_amdgcn_readfirstlane(s_count);
+    evals += (unsigned long long)S;
+    rounds = (S + 127) / 128;
+    if (rounds > 0) fetch_rows(0, 0);
+    return true;
+  };
+  auto point_end = [&]() {
+    int btid = tid;
+    asm volatile("" : "+v"(btid));
+    __syncthreads();                                        // every wave's entries of vis_tab
+    if (btid < L) {
+      const float* w = a.wdir + dbase + (long)btid * nsamp;
+      float acc = 0.f;
+      for (int k = 0; k < nsamp; ++k) acc += vis_tab[btid * nsamp + k] * w[k];
+      a.vis_out[p * L + btid] = acc / a.wsum[(a.cid ? a.cid[p] : 0) * L + btid];
+    }
+  };
   long rd = STREAM ? (long)blockIdx.x : 0L;
-  const long rd_end = STREAM ? total_rounds : (long)rounds, rd_step = STREAM ? (long)G : 1L;
+  long rd_end = STREAM ? total_rounds : 0L;
+  const long rd_step = STREAM ? (long)G : 1L;
   int parity = 0;
-  if constexpr (STREAM) tile_lookup(rd);
-  if (rounds > 0) fetch_rows(rd, 0);
+  if constexpr (STREAM) {
+    tile_lookup(rd);
+    fetch_rows(rd, 0);
+  }
 #ifdef XT_TIMING   // phase stamps (tools/build_variant.sh ... -DXT_TIMING): profiles/r05_dvis_f16_phases.md
 #define XT_T(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc[i] += t_ - tlast; tlast = t_; }
   unsigned long long tacc[4] = {0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
   int trounds = 0;
+  // per-point form: the three parts of a point in 10 ns ticks of the constant clock, summed over the workgroup's points
+  // (profiles/dvis_persistent_ab.md): boundary up to the first conversion | the rounds | barrier + reduce
+#define XT_PT(i) { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); ptacc[i] += t_ - ptlast; ptlast = t_; }
+  unsigned long long ptacc[3] = {0, 0, 0}, ptlast = __builtin_amdgcn_s_memrealtime();
+  const unsigned long long pt_first = ptlast;
+  int tpoints = 0;
 #else
 #define XT_T(i)
+#define XT_PT(i)
 #endif
   {
     // A round with NT live tiles per wave.  NT = 1 (per-point form): the last round of a point when it holds at most 64 samples,
@@ -676,48 +750,62 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
       }
     }
     };
-    // the stream form's rounds stay two-tile: only the last round of a launch could be one-tile there
-    const bool tail1 = !STREAM && XT_FP8 && rounds > 0 && S - (rounds - 1) * 128 <= 64;     // workgroup-uniform
-    const long rd_end2 = tail1 ? rd_end - 1 : rd_end;
-    for (; rd < rd_end2; rd += rd_step) {
-      if constexpr (STREAM) tile_lookup(rd + rd_step);
+    // the per-point form's loop over the points it takes from the queue; the stream form passes once
+    for (;;) {
+      if constexpr (!STREAM) {
+        if (!point_begin()) break;
+        rd = 0, rd_end = (long)rounds;
 #ifdef XT_TIMING
-      ++trounds;
+        ++tpoints;
+        tlast = __builtin_amdgcn_s_memtime();
 #endif
-      XT_T(3)
-      round_body(XtInt<2>{});
-      parity ^= 1;
-      XT_T(2)
-    }
-    if constexpr (!STREAM && XT_FP8) {
-      if (tail1) {
+        XT_PT(0)
+      }
+      // the stream form's rounds stay two-tile: only the last round of a launch could be one-tile there
+      const bool tail1 = !STREAM && XT_FP8 && rounds > 0 && S - (rounds - 1) * 128 <= 64;     // workgroup-uniform
+      const long rd_end2 = tail1 ? rd_end - 1 : rd_end;
+      for (; rd < rd_end2; rd += rd_step) {
+        if constexpr (STREAM) tile_lookup(rd + rd_step);
 #ifdef XT_TIMING
         ++trounds;
 #endif
         XT_T(3)
-        round_body(XtInt<1>{});
+        round_body(XtInt<2>{});
+        parity ^= 1;
         XT_T(2)
       }
+      if constexpr (!STREAM && XT_FP8) {
+        if (tail1) {
+#ifdef XT_TIMING
+          ++trounds;
+#endif
+          XT_T(3)
+          round_body(XtInt<1>{});
+          XT_T(2)
+        }
+      }
+      if constexpr (STREAM) break;
+      XT_PT(1)
+      point_end();
+      XT_PT(2)
     }
   }
 #ifdef XT_TIMING
-  if ((blockIdx.x == 7 || blockIdx.x == 4000) && tid == 0 && trounds > 0)
+  if ((STREAM ? blockIdx.x == 7 || blockIdx.x == 4000 : (blockIdx.x & 31) == 7) && tid == 0 && trounds > 0)
     printf("x6t wg %d rounds %d cycles/round: conv %llu layers %llu head+fetch %llu lookup %llu\n", (int)blockIdx.x, trounds, tacc[0] / trounds,
            tacc[1] / trounds, tacc[2] / trounds, tacc[3] / trounds);
+  if (!STREAM && (blockIdx.x & 31) == 7 && tid == 0 && tpoints > 0)
+    printf("x6t wg %d points %d rounds %d ticks(10 ns) in all: boundary %llu rounds %llu reduce %llu workgroup %llu\n", (int)blockIdx.x, tpoints,
+           trounds, ptacc[0], ptacc[1], ptacc[2], __builtin_amdgcn_s_memrealtime() - pt_first);
 #endif
 #undef XT_MFMA
   range_report<true>(sat, a.range_word);
+  if constexpr (!STREAM) {
+    if (tid == 0 && a.eval_count) atomicAdd(a.eval_count, evals);
+  }
   // drain the ring (copies still target this workgroup's LDS)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (!STREAM) {
-    if (tid < L) {
-      const float* w = a.wdir + dbase + (long)tid * nsamp;
-      float acc = 0.f;
-      for (int k = 0; k < nsamp; ++k) acc += vis_tab[tid * nsamp + k] * w[k];
-      a.vis_out[p * L + tid] = acc / a.wsum[(a.cid ? a.cid[p] : 0) * L + tid];
-    }
-  }
 }
 
 // the cull / per-lobe reduce passes around the stream form: precision-agnostic (dvis_tiles.hip), shared with the legacy split-precision family
@@ -732,6 +820,37 @@ __global__ void k_dvis3_reduce(const int* __restrict__ cid, long n, const float*
 }  // namespace rb
 
 using namespace rb;
+
+// The point queues of the per-point form: library-internal device words (as range_flags()), one block per device, allocated at the
+// first launch there.  A launch takes the next word of the block in turn and zeroes it on its stream in front of the kernel, so
+// launches that overlap on different streams do not share a counter unless XT_QUEUES of them are in flight at one time.
+constexpr int XT_QUEUES = 256, XT_MAX_DEVICES = 64;
+static unsigned* g_pt_queues[XT_MAX_DEVICES] = {};
+static std::atomic<unsigned> g_pt_turn{0};
+static std::mutex g_pt_mutex;
+static unsigned* pt_queue() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= XT_MAX_DEVICES) return nullptr;
+  std::lock_guard<std::mutex> lock(g_pt_mutex);
+  if (!g_pt_queues[dev]) {
+    void* d = nullptr;
+    if (hipMalloc(&d, XT_QUEUES * sizeof(unsigned)) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    g_pt_queues[dev] = static_cast<unsigned*>(d);
+  }
+  return g_pt_queues[dev] + g_pt_turn.fetch_add(1u) % XT_QUEUES;
+}
+
+// Workgroups of the persistent grid: 0 = one per compute unit, unless ROBIR_DVIS_PT_WORKGROUPS names a number (tests, A/B runs).  Read at
+// every launch, so that ops.DVIS_PT_WORKGROUPS can change it between two launches; an entry point of its own would not fit the
+// header (tests/test_abi_cpu.py bounds its symbol count at the 100 it holds).
+static int pt_workgroups() {
+  const char* e = getenv("ROBIR_DVIS_PT_WORKGROUPS");
+  const int w = e ? atoi(e) : 0;
+  return w > 0 ? w : 0;
+}
 
 extern "C" int rb_dvis_fused_x6t(const float* normals, const int* chunk_id, long n, const float* A, const float* Bd,
                                  const float* dirs, const float* wdir, const float* wsum, const float* W49, int L, int nsamp,
@@ -751,7 +870,12 @@ extern "C" int rb_dvis_fused_x6t(const float* normals, const int* chunk_id, long
   a.range_word = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
   a.normals = normals, a.dirs = dirs, a.wdir = wdir, a.wsum = wsum, a.cid = chunk_id, a.L = L, a.nsamp = nsamp;
   a.vis_out = vis_out, a.eval_count = eval_count;
-  hipLaunchKernelGGL(k_dvis_x6t<false>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
+  const int grid = persistent_grid(n, pt_workgroups());      // min(n, workgroups); 0 workgroups = one per compute unit
+  RB_REQUIRE(grid > 0, "device query failed");
+  a.n = n, a.queue = pt_queue();
+  RB_REQUIRE(a.queue, "no device memory for the point queue");
+  if (hipMemsetAsync(a.queue, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return rb::fail(__func__, "memset failed");
+  hipLaunchKernelGGL(k_dvis_x6t<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("k_dvis_x6t");
 }
 

@@ -666,6 +666,10 @@ DVIS_KERNEL_NAMES = {"fp32": "k_dvis_fused<fp32>", "f16x6": "k_dvis_x6t", "f16x6
 
 
 DVIS_STREAM_WORKGROUPS = 0        # persistent workgroups of the streaming visibility kernel; 0 = one per compute unit
+# persistent workgroups of the per-point form (rb_dvis_fused_x6t); 0 = one per compute unit.  The library reads the environment variable at
+# every launch (include/robir_hip.h): dvis_fused writes a changed value back to it
+DVIS_PT_WORKGROUPS = int(os.environ.get("ROBIR_DVIS_PT_WORKGROUPS") or 0)
+_dvis_pt_workgroups_env = DVIS_PT_WORKGROUPS
 DVIS_STREAM_MAX_POINTS = 8192     # launches up to this many surface points take the tile-list (streaming) form
 DVIS_STREAM_SHORT_LIST = 1024     # ... and any launch whose points have at most this many sampled directions (L * nsamp)
 # the f16 throughput mode's kernel: 3 = the point-block form (csrc/vis_diffuse_f16p.hip: sixteen points x one direction per tile; needs
@@ -724,6 +728,11 @@ def dvis_fused(normals, chunk_id, A, Bd, dirs, wdir, wsum, split, L, nsamp, argm
         point_info = torch.empty(n, 2, dtype=torch.int32, device=dev)
         counters = torch.empty(2, dtype=torch.int64, device=dev)
         args += [ptr(pair_j), ptr(pair_vis), ptr(tile_info), ptr(point_info), ptr(counters), c_int(DVIS_STREAM_WORKGROUPS)]
+    elif r.entry == "rb_dvis_fused_x6t":      # persistent grid: its size reaches the library through the environment, written when it changes
+        global _dvis_pt_workgroups_env
+        if int(DVIS_PT_WORKGROUPS) != _dvis_pt_workgroups_env:
+            _dvis_pt_workgroups_env = int(DVIS_PT_WORKGROUPS)
+            os.environ["ROBIR_DVIS_PT_WORKGROUPS"] = str(max(0, _dvis_pt_workgroups_env))
     (_lib.call_legacy if r.legacy else call)(r.entry, *args, ptr(out), ptr(eval_count), stream_ptr())
     if r.layout == "pblock" and os.environ.get("ROBIR_RANGE_CHECK", "") == "sync" and int(counters[3].item()) != 0:
         # counters[3]: chunk ids not ascending (a list whose order was only ASSERTED through the `_robir_ascending` attribute) or more
