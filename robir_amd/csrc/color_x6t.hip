@@ -5,7 +5,9 @@
 // two k-blocks; K = 256 after: two parts of four) through a 4-slot LDS ring of 30 KB slots, all biases resident in the LDS, rounds of
 // 128 rows, the copies of the chunk three ahead first and the previous chunk's relu + exact three-way split behind them, the rgb rows
 // through a per-round buffer descriptor.  The products of a class are summed part by part: results agree with k_color_x6 to fp32
-// summation order.  The host mirror takes this kernel where it needs fewer than two thirds of the one-tile form's passes (ops.sdf_two_tile).
+// summation order.  The layer loop is this kernel's own on the shared pieces of x6t_engine.h (bias table, xt_wait, xt_barrier,
+// xt_refill, xt_copy_ahead, xt_prologue; with xt_rotate, or under one loop for the three kernels, its spills move:
+// profiles/x6t_layer_refactor.md).  The host mirror takes this kernel where it needs fewer than two thirds of the one-tile form's passes (ops.sdf_two_tile).
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
@@ -34,7 +36,6 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   if ((long)blockIdx.x >= nrounds) return;
 
   const float negk = -2048.0f;
-  constexpr float C11 = 1.0f / 2048.0f;
   const unsigned ring_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)ring);
   unsigned ring_lane = ring_b + (unsigned)lane * 16u;
   asm volatile("" : "+v"(ring_lane));
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   long round = 0;
   __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(rgb, 0, 0, 0x00020000);
 
-  for (int i = tid; i < CT_NCHUNK * 4; i += 256) bias_tab[i] = Wp[CtStream::coff(i >> 2) + (i & 3)];
+  xt_load_bias<CtStream>(bias_tab, Wp, tid);
 
   // NONNEG: relu outputs (>= 0: the raw pattern of the h piece orders like the value, one instruction: mlp_engine.h)
   unsigned sat_in = 0u;                // ... of a round's signed inputs (sat_acc's domain): folded into `sat` at the end of the input stage
@@ -135,9 +136,9 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   auto run_layer = [&](auto LI_tag, int cb) {
     constexpr int LI = decltype(LI_tag)::value;
     constexpr int K = CtNet::K(LI), NCH = CtNet::nch(LI), CB = 16 * LI;
-    constexpr int WK = xt_wk(K), NPART = xt_parts(K), NFREE = 9 * NPART;
+    constexpr int NPART = xt_parts(K), NFREE = 9 * NPART;
     constexpr bool OUT = LI == 4;
-    constexpr int WKN = xt_wk(CtNet::K(LI == 4 ? 0 : LI + 1));
+    constexpr int KN = CtNet::K(LI == 4 ? 0 : LI + 1);
     static_assert((NCH * NPART) % 2 == 0, "a layer has an even number of parts");
     SxAcc acc[2], prev[2];
     const f4* wl = Wp + CtStream::coff(cb);
@@ -145,15 +146,11 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 3; ++i) wnext[i] = Wp + CtStream::coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
-    auto bias_of = [&](int c) {
-      const int cc = c >= CT_NCHUNK ? c - CT_NCHUNK : c;
-      return bias_tab[cc * 4 + g];
-    };
-    auto combine = [&](const SxAcc& a, int r) { return __builtin_fmaf(__builtin_fmaf(a.c2[r], C11, a.c1[r]), C11, a.c0[r]); };
+    auto bias_of = [&](int c) { return xt_bias_of<CtStream>(bias_tab, c, g); };
     float z[2][4];
     auto item_z = [&](int t, const SxAcc& a) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) z[t][r] = fmaxf(combine(a, r), 0.f);
+      for (int r = 0; r < 4; ++r) z[t][r] = fmaxf(sx_combine(a, r), 0.f);
     };
     // epilogue items of hidden chunk pj: the second tile's combine + relu (the first tile's went behind the chunk's own last run), then
     // the exact three-way split of the four value pairs into the next layer's operand registers
@@ -171,25 +168,18 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
     for (int jb = 0; jb < NCH; ++jb) {
       // chunk jb+1 has landed once at most this wave's copies of chunk jb+2 are in flight; past the barrier every wave has finished with
       // chunk jb-1, whose slot the copies of chunk jb+3 reuse
-      constexpr int dummy = 0;
-      (void)dummy;
       const int K2 = jb + 2 < NCH ? K : CtNet::K(CtStream::layer_of(CB + jb + 2));
-      if (sx_nsw(K2) >= 8) sx_wait<8>();
-      else sx_wait<6>();
-#ifndef CT_ABL_NOBAR                   // timing ablations (wrong results): no per-chunk barrier | no epilogue | no copies | no fragment reads
-      __builtin_amdgcn_s_barrier();
-#endif
-      asm volatile("" ::: "memory");
+      xt_wait(sx_nsw(K2));
+      xt_barrier();
       const int K3 = jb + 3 < NCH ? K : CtNet::K(CtStream::layer_of(CB + jb + 3));
       const int NC3 = sx_nsw(K3);
       const int f3 = span_first(K3);
       const f4* src3 = (jb + 3 < NCH ? wl + (long)(jb + 3) * sx_cf4(K) : wnext[jb + 3 - NCH < 3 ? jb + 3 - NCH : 0]) + 4 + f3 * 64;
       const unsigned dst3 = ring_b + slot_b[(jb + 3) & 3] + (unsigned)f3 * 1024u;
       f4 nbias;
-      acc[0].c0 = bias;
-      acc[1].c0 = bias;
-      acc[0].c1 = acc[0].c2 = acc[1].c1 = acc[1].c2 = f4{0.f, 0.f, 0.f, 0.f};
-#ifdef CT_ABL_NOEP
+      sx_zero_acc(acc[0], bias);
+      sx_zero_acc(acc[1], bias);
+#ifdef CT_ABL_NOEP                     // timing ablation (wrong results): no epilogue
       const int ne = 0;
 #else
       const int ne = (jb > 0 && !OUT) ? NE : 0;
@@ -201,33 +191,12 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
         if (a < 0) return;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-#ifndef CT_ABL_NODMA
-          if (i < NC3 && i == a) xt_copy_piece_seq(i, src3, dst3, lv);            // the copies first
-#endif
+          if (i < NC3 && i == a) xt_copy_ahead(i, src3, dst3, lv);            // the copies first
 #pragma unroll
         for (int i = 0; i < NE; ++i)
           if (i < ne && NC3 + xt_item_slot(i, NE, NFREE - NC3) == a) ep_item(i, jb > 0 ? jb - 1 : 0);
       };
-      auto refill = [&](int piece, int part) {
-        const bool down = ((jb * NPART + part) & 1) != 0;
-        int slot, kb_first, count;
-        if (part + 1 < NPART) {
-          slot = jb & 3, kb_first = (part + 1) * WK, count = WK;
-        } else {
-          slot = (jb + 1) & 3, kb_first = 0, count = jb + 1 < NCH ? WK : WKN;
-        }
-#ifdef CT_ABL_NOREAD
-        {
-          u4(&d)[4] = piece == 0 ? win.h : (piece == 1 ? win.m : win.l);
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (k < count) asm volatile("" : "+v"(d[k]));
-          (void)slot; (void)kb_first; (void)down;
-        }
-#else
-        xt_request(piece == 0 ? win.h : (piece == 1 ? win.m : win.l), ring_lane + slot_b[slot], kb_first, count, piece, down);
-#endif
-      };
+      auto refill = [&](int piece, int part) { xt_refill<K, KN, NCH>(win, ring_lane, slot_b, jb, piece, part); };
       xt_chunk<K, 10>(jb * NPART, acc, win, P, filler, refill);
       if constexpr (OUT) prev[0] = acc[0];
       else item_z(0, acc[0]);
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
         asm volatile("" : "+v"(base));
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float v = 1.0f / (1.0f + expf(-combine(prev[t], c)));
+          const float v = 1.0f / (1.0f + expf(-sx_combine(prev[t], c)));
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, base, c * 4, 0);
         }
       }
@@ -269,16 +238,7 @@ __global__ __launch_bounds__(256, 1) void k_color_x6t(const float* __restrict__ 
   };
 
   // ---- prologue: chunks 0, 1, 2 of the stream (layer 0: K = 320, eight pieces per wave), the first fragment window
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      xt_copy_piece(i, Wp + CtStream::coff(c) + 4 + first320 * 64, ring_b + slot_b[c] + (unsigned)first320 * 1024u);
-  sx_wait<0>();
-  __syncthreads();
-  xt_request(win.h, ring_lane + slot_b[0], 0, 2, 0, true);
-  xt_request(win.m, ring_lane + slot_b[0], 0, 2, 1, true);
-  xt_request(win.l, ring_lane + slot_b[0], 0, 2, 2, true);
+  xt_prologue<CtStream, 320>(Wp, ring_b, ring_lane, slot_b, first320, win);
 
   for (round = blockIdx.x; round < nrounds; round += gridDim.x) {
     {

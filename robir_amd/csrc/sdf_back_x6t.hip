@@ -13,6 +13,8 @@
 // registers); two tiles have no room for that: the gate of a (tile, chunk) -- 1 KB -- rides the weight stream as one more LDS-DMA
 // piece per tile and chunk into a wave-private LDS slot (three chunks ahead, like the weights: it comes from HBM), so every chunk
 // issues the same eight copies per wave and the counted waits stay exact.  Weights: packing.pack_sdf_back_x6(two_tile=True).
+// The layer loop is this kernel's own on the shared pieces of x6t_engine.h (xt_wait, xt_barrier, xt_refill, xt_copy_ahead, xt_rotate;
+// with xt_prologue, or under one loop for the three kernels, its register allocation moves: profiles/x6t_layer_refactor.md).
 #include "../../include/robir_hip.h"
 #include "common.h"
 #include "mlp_engine.h"
@@ -38,7 +40,6 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
   if ((long)blockIdx.x >= nrounds) return;
 
   const float negk = -2048.0f, inv_sqrt2 = 0.70710678118654752440f;
-  constexpr float C11 = 1.0f / 2048.0f;
   const unsigned ring_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)ring);
   const unsigned gate_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)gate_ring) + (unsigned)wave * 12288u;
   unsigned ring_lane = ring_b + (unsigned)lane * 16u;                  // + slot + fragment offset: the fragment reads
@@ -102,19 +103,18 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
   // gate: sigmoid layer that gates this stream layer's outputs (stream layers 0..6: 6 - l); gate_next: ... the next stream layer's
   auto run_layer = [&](auto LI_tag, int cb, int gate, int gate_next) {
     constexpr int LI = decltype(LI_tag)::value;      // 0: hidden (stream layers 0, 1, 2, 4, 5, 6), 3: W4^T (gate + skip rows), 7: W0^T (outputs)
-    constexpr int K = 256, NCH = BtNet::nch(LI), WK = 4, NPART = 2, NFREE = 18;
+    constexpr int K = 256, NCH = BtNet::nch(LI), NPART = 2, NFREE = 18;
     constexpr bool OUT = LI == 7, SKIPL = LI == 3;
     SxAcc acc[2], prev[2];
     const f4* wl = Wt + BtStream::coff(cb);
     asm volatile("" : "+s"(wl));
-    auto combine = [&](const SxAcc& a, int r) { return __builtin_fmaf(__builtin_fmaf(a.c2[r], C11, a.c1[r]), C11, a.c0[r]); };
     float z[2][4];
     f4 gt[2];       // the gates of the chunk whose epilogue is running, both tiles: read with the first item -- a read placed beside its use
                     // waits with lgkmcnt(0), i.e. for every fragment request in flight
     auto item_z = [&](int t, const SxAcc& a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        z[t][r] = combine(a, r);
+        z[t][r] = sx_combine(a, r);
         if (SKIPL) z[t][r] *= inv_sqrt2;
       }
     };
@@ -153,11 +153,8 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
 #pragma unroll
     for (int jb = 0; jb < NCH; ++jb) {
       // chunk jb+1 (and the gates of chunk jb) have landed once at most the eight copies issued during chunk jb-1 are in flight
-      sx_wait<8>();
-#ifndef BT_NOBAR
-      __builtin_amdgcn_s_barrier();
-#endif
-      asm volatile("" ::: "memory");
+      xt_wait(sx_nsw(K) + 2);
+      xt_barrier();
       const f4* src3 = wl + (long)(jb + 3) * sx_cf4(256) + 4 + first * 64;       // the stream is uniform: chunk cb + jb + 3, cyclic
       if (cb + jb + 3 >= BT_NCHUNK) src3 -= (long)BT_NCHUNK * sx_cf4(256);
       const unsigned dst3 = ring_b + slot_b[(jb + 3) & 3] + (unsigned)first * 1024u;
@@ -166,7 +163,8 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
       const int g_layer = nl ? gate_next : ((OUT || (SKIPL && jb + 3 >= 13)) ? -1 : gate);
       const int g_chunk = nl ? jb + 3 - NCH : jb + 3;
       const unsigned g_slot = gslot_b[(jb + 3) % 6];
-      acc[0].c0 = acc[1].c0 = acc[0].c1 = acc[0].c2 = acc[1].c1 = acc[1].c2 = f4{0.f, 0.f, 0.f, 0.f};
+      sx_zero_acc(acc[0], f4{0.f, 0.f, 0.f, 0.f});
+      sx_zero_acc(acc[1], f4{0.f, 0.f, 0.f, 0.f});
       const int ne = jb > 0 ? NE : 0, ni = ne + 8;
       const unsigned ep_gslot = gslot_b[(jb + 5) % 6];    // = slot of chunk jb-1
       unsigned lv = 0u;             // lane offset of this chunk's copies, carried from piece to piece (x6t_engine.h)
@@ -178,28 +176,21 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
           if (i < ni && xt_item_slot(i, ni, NFREE) == a) {
             if (i < ne) ep_item(i, jb - 1, ep_gslot);
             else if (i - ne < 2) gate_copy(i - ne, g_layer, g_chunk, g_slot, nl && LI == 7, lv);
-            else xt_copy_piece_seq(i - ne - 2, src3, dst3, lv, true);
+            else xt_copy_ahead(i - ne - 2, src3, dst3, lv, true);
           }
       };
-      auto refill = [&](int piece, int part) {
-        const bool down = ((jb * NPART + part) & 1) != 0;
-        const int slot = part == 0 ? (jb & 3) : ((jb + 1) & 3), kb_first = part == 0 ? WK : 0;
-        xt_request(piece == 0 ? win.h : (piece == 1 ? win.m : win.l), ring_lane + slot_b[slot], kb_first, WK, piece, down);
-      };
+      auto refill = [&](int piece, int part) { xt_refill<K, K, NCH>(win, ring_lane, slot_b, jb, piece, part); };
       xt_chunk<K, 8>(jb * NPART, acc, win, P, filler, refill);
       item_z(0, acc[0]);
       prev[1] = acc[1];
     }
     const unsigned last_gslot = gslot_b[(NCH - 1) % 6];
-    {   // slot 0 = the slot of the next layer's first chunk
-      constexpr int R = NCH & 3, R6 = NCH % 6;
-      unsigned a[4], b[6];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = slot_b[(i + R) & 3];
+    xt_rotate<NCH & 3>(slot_b);
+    {   // gate slot 0 = the gate slot of the next layer's first chunk
+      constexpr int R6 = NCH % 6;
+      unsigned b[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) b[i] = gslot_b[(i + R6) % 6];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) slot_b[i] = a[i];
 #pragma unroll
       for (int i = 0; i < 6; ++i) gslot_b[i] = b[i];
     }

@@ -15,7 +15,10 @@
 // MODE 0: signed distance only -> out0[M].   MODE 1: all 257 outputs -> out0[M,257].   MODE 5: MODE 1 + sigmoid(100 z) of every hidden
 // pre-activation -> sig [tile = row / 16][layer 8][chunk 16][lane 64] float4, the layout k_sdf_back_* read.
 // The products of a class are summed part by part, not product by product over the whole chunk as in k_sdf_x6: another fp32 summation
-// order, results differ from the one-tile kernel's in the last bits.  (A K-major form of the hidden 256 x 256 layers with the epilogue cut
+// order, results differ from the one-tile kernel's in the last bits.  The layer loop below is this kernel's own, on the pieces the
+// three two-tile stream kernels share (x6t_engine.h: bias table, xt_wait, xt_barrier, xt_refill, xt_copy_ahead, xt_rotate, xt_prologue;
+// one loop for the three, xt_layer, moved this kernel's spills: profiles/x6t_layer_refactor.md -- as does removing the dead sat_in /
+// fold_sat_in pair below, which therefore stays).  (A K-major form of the hidden 256 x 256 layers with the epilogue cut
 // into single-instruction steps saved 1.6 % per round and nothing on value + gradient, and was removed: profiles/r06_sdf_fine_phases.md.)
 #include "../../include/robir_hip.h"
 #include "common.h"
@@ -45,7 +48,6 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   if ((long)blockIdx.x >= nrounds) return;
 
   const float negk = -2048.0f, inv_sqrt2 = 0.70710678118654752440f;
-  constexpr float C11 = 1.0f / 2048.0f;
   const unsigned ring_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)ring);
   unsigned ring_lane = ring_b + (unsigned)lane * 16u;                  // + slot + fragment offset: the fragment reads
   asm volatile("" : "+v"(ring_lane));
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   long round = 0;
   auto row_of = [&](int t) { return round * 128 + t * 64 + rlocal; };
 
-  for (int i = tid; i < NCHUNK * 4; i += 256) bias_tab[i] = Wp[Stream::coff(i >> 2) + (i & 3)];
+  xt_load_bias<Stream>(bias_tab, Wp, tid);
 
   // range sentinel: `sat` in the domain of sat_acc_nonneg (softplus outputs are >= 0: the raw pattern of the h piece orders like the value,
   // one instruction per pair); the signed inputs of a round (encoded rows) go through sat_acc into `sat_in`, folded into `sat` behind them
@@ -127,9 +129,9 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   auto run_layer = [&](auto LI_tag, int cb, int lrt) {
     constexpr int LI = decltype(LI_tag)::value;
     constexpr int K = Net::K(LI), NCH = Net::nch(LI), CB = Stream::cbase(LI);
-    constexpr int WK = xt_wk(K), NPART = xt_parts(K), NFREE = 9 * NPART;
+    constexpr int NPART = xt_parts(K), NFREE = 9 * NPART;
     constexpr bool OUT = LI == 8, SKIPOUT = LI == 3;
-    constexpr int KN = Net::K(LI == 8 ? 0 : LI + 1), WKN = xt_wk(KN);
+    constexpr int KN = Net::K(LI == 8 ? 0 : LI + 1);
     static_assert((NCH * NPART) % 2 == 0, "a layer has an even number of parts");
     constexpr int PNCH = Net::nch(LI == 0 ? 8 : LI - 1);      // chunks of the layer that runs before this one (layer 8 of the previous round)
     // stores of the epilogue of chunk pj (pj < 0: no such chunk) of an output / a hidden layer
@@ -145,11 +147,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
 #pragma unroll
     for (int i = 0; i < 3; ++i) wnext[i] = Wp + Stream::coff(cb + NCH + i);
     asm volatile("" : "+s"(wl));
-    auto bias_of = [&](int c) {      // c = stream position (may run past the end once)
-      const int cc = c >= NCHUNK ? c - NCHUNK : c;
-      return bias_tab[cc * 4 + g];
-    };
-    auto combine = [&](const SxAcc& a, int r) { return __builtin_fmaf(__builtin_fmaf(a.c2[r], C11, a.c1[r]), C11, a.c0[r]); };
+    auto bias_of = [&](int c) { return xt_bias_of<Stream>(bias_tab, c, g); };
     // epilogue of hidden chunk pj, twelve items: per value pair (tile t, register pair q) A0 / A1 = softplus (+ its sigmoid in MODE 5) of
     // its two values, B = exact three-way split into the next layer's operand registers (+ the tile's sigmoid store behind its second pair)
     float ev[4][2];
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
     // Z = the three classes of a tile's four values combined (frees the previous chunk's accumulators early)
     auto item_z = [&](int t, const SxAcc& a) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) z[t][r] = combine(a, r);
+      for (int r = 0; r < 4; ++r) z[t][r] = sx_combine(a, r);
     };
     // sk: the chunk's layer feeds the skip concatenation (its outputs / sqrt 2); lr: that layer's index (sigmoid tiles); Y: the operand
     // set the split writes (the next layer's -- or, for a chunk finished across the layer boundary, the running layer's own inputs)
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
       asm volatile("" : "+v"(base));
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = combine(prev[t], r) * out_scale;
+        const float v = sx_combine(prev[t], r) * out_scale;
         if constexpr (FULL) {
           if (pj < 16) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, base, pj * 64 + r * 4, 0);
           else if (r == 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rsrc, g == 0 ? base : -1, pj * 64, 0);
@@ -248,8 +246,6 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
     for (int jb = 0; jb < NCH; ++jb) {
       // chunk jb+1 has landed once at most this wave's copies of chunk jb+2 are in flight (stores of the epilogue, younger, only make the
       // wait stricter); past the barrier every wave has finished with chunk jb-1, whose slot the copies of chunk jb+3 reuse
-      constexpr int dummy = 0;
-      (void)dummy;
       const int K2 = jb + 2 < NCH ? K : Net::K(Stream::layer_of(CB + jb + 2));
       // ... plus the stores of the epilogue items that ran beside them (exact: every store is issued, lanes out of range are dropped by
       // the descriptor): the previous chunk carried the epilogue of the chunk before it; a layer's first chunk follows the previous
@@ -259,45 +255,16 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
       else if (jb == 2) ns = ep_stores(OUT, jb - 2);
       else if (jb == 1) ns = PEND ? ep_stores(false, 0) : 0;          // chunk 0 carried the previous layer's pending last chunk
       else ns = ep_stores(LI == 0, PNCH - 2) + (LI == 0 ? ep_stores(true, PNCH - 1) : 0);      // an output layer finishes its last chunk at once
-      switch (sx_nsw(K2) + ns) {
-        case 2: sx_wait<2>(); break;
-        case 3: sx_wait<3>(); break;
-        case 4: sx_wait<4>(); break;
-        case 5: sx_wait<5>(); break;
-        case 6: sx_wait<6>(); break;
-        case 7: sx_wait<7>(); break;
-        case 8: sx_wait<8>(); break;
-        case 9: sx_wait<9>(); break;
-        case 10: sx_wait<10>(); break;
-        case 11: sx_wait<11>(); break;
-        case 12: sx_wait<12>(); break;
-        case 13: sx_wait<13>(); break;
-        case 14: sx_wait<14>(); break;
-        case 15: sx_wait<15>(); break;
-        case 16: sx_wait<16>(); break;
-        case 17: sx_wait<17>(); break;
-        case 18: sx_wait<18>(); break;
-        case 19: sx_wait<19>(); break;
-        case 20: sx_wait<20>(); break;
-        case 21: sx_wait<21>(); break;
-        case 22: sx_wait<22>(); break;
-        case 23: sx_wait<23>(); break;
-        case 24: sx_wait<24>(); break;
-        default: sx_wait<2>(); break;      // any combination not listed: the strictest wait (safe)
-      }
-#ifndef SXT_NOBAR
-      __builtin_amdgcn_s_barrier();
-#endif
-      asm volatile("" ::: "memory");
+      xt_wait(sx_nsw(K2) + ns);
+      xt_barrier();
       const int K3 = jb + 3 < NCH ? K : Net::K(Stream::layer_of(CB + jb + 3));
       const int NC3 = sx_nsw(K3);
       const int f3 = span_first(K3);
       const f4* src3 = (jb + 3 < NCH ? wl + (long)(jb + 3) * sx_cf4(K) : wnext[jb + 3 - NCH < 3 ? jb + 3 - NCH : 0]) + 4 + f3 * 64;
       const unsigned dst3 = ring_b + slot_b[(jb + 3) & 3] + (unsigned)f3 * 1024u;
       f4 nbias;
-      acc[0].c0 = bias;
-      acc[1].c0 = bias;
-      acc[0].c1 = acc[0].c2 = acc[1].c1 = acc[1].c2 = f4{0.f, 0.f, 0.f, 0.f};
+      sx_zero_acc(acc[0], bias);
+      sx_zero_acc(acc[1], bias);
       const int ne = jb > 0 ? NE : 0, ni = ne + NC3;
       ep_voff_adj = NC3 > 4 ? 4096 : 0;
       auto filler = [&](int pos) {
@@ -317,11 +284,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
             }
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            if (i < NC3 && 9 + xt_item_slot(i, NC3, NFREE - 9) == a) {
-#ifndef SXT_NODMA
-              xt_copy_piece_seq(i, src3, dst3, lv);
-#endif
-            }
+            if (i < NC3 && 9 + xt_item_slot(i, NC3, NFREE - 9) == a) xt_copy_ahead(i, src3, dst3, lv);
           return;
         }
         // the copies take the chunk's first free positions, the epilogue items the rest: a store of the epilogue is then younger than
@@ -334,38 +297,18 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
               ep_own_voff = NC3 == 0;
               if (jb > 0) ep_item(i, jb - 1);
             } else {
-#ifndef SXT_NODMA
-              xt_copy_piece_seq(i - ne, src3, dst3, lv);
-#endif
+              xt_copy_ahead(i - ne, src3, dst3, lv);
             }
           }
       };
-      auto refill = [&](int piece, int part) {
-        const bool down = ((jb * NPART + part) & 1) != 0;
-        int slot, kb_first, count;
-        if (part + 1 < NPART) {
-          slot = jb & 3, kb_first = (part + 1) * WK, count = WK;
-        } else {
-          slot = (jb + 1) & 3, kb_first = 0, count = jb + 1 < NCH ? WK : WKN;
-        }
-#ifndef SXT_NOREAD
-        xt_request(piece == 0 ? win.h : (piece == 1 ? win.m : win.l), ring_lane + slot_b[slot], kb_first, count, piece, down);
-#endif
-      };
+      auto refill = [&](int piece, int part) { xt_refill<K, KN, NCH>(win, ring_lane, slot_b, jb, piece, part); };
       xt_chunk<K, 9>(jb * NPART, acc, win, P, filler, refill);
       if constexpr (OUT) prev[0] = acc[0];
       else item_z(0, acc[0]);
       prev[1] = acc[1];
       bias = nbias;
     }
-    {   // slot 0 = the slot of the next layer's first chunk
-      constexpr int R = NCH & 3;
-      unsigned a[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = slot_b[(i + R) & 3];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) slot_b[i] = a[i];
-    }
+    xt_rotate<NCH & 3>(slot_b);
     if constexpr (OUT) {      // hidden layers leave their last chunk (z[0], prev[1]) to the next layer's first chunk
 #pragma unroll
       for (int s = 0; s < NE; ++s) ep_item(s, NCH - 1);
@@ -390,16 +333,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_x6t(const float* __restrict__ xy
   };
 
   // ---- prologue: chunks 0, 1, 2 of the stream (layer 0: K = 64, two pieces per wave), the first fragment window
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      xt_copy_piece(i, Wp + Stream::coff(c) + 4 + first64 * 64, ring_b + slot_b[c] + (unsigned)first64 * 1024u);
-  sx_wait<0>();
-  __syncthreads();
-  xt_request(win.h, ring_lane + slot_b[0], 0, 2, 0, true);
-  xt_request(win.m, ring_lane + slot_b[0], 0, 2, 1, true);
-  xt_request(win.l, ring_lane + slot_b[0], 0, 2, 2, true);
+  xt_prologue<Stream, 64>(Wp, ring_b, ring_lane, slot_b, first64, win);
 
 #ifdef SXT_TIMING   // phase stamps per round (tools/build_variant.sh ... -DSXT_TIMING; profiles/r05_sdf_phases.md)
 #define SXT_T(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc[i] += t_ - tlast; tlast = t_; }

@@ -13,6 +13,13 @@
 // alternate the direction in which they walk the window, so a part starts with the fragment requested LAST: one s_waitcnt covers the
 // window (fragments return in order).  Every layer of the nets built on this has an even number of parts, so a layer starts upwards.
 // Between the runs go the "fillers": the LDS-DMA copies of the chunk three ahead, the staged epilogue of the previous chunk.
+//
+// sdf_x6t.hip, color_x6t.hip and sdf_back_x6t.hip run the nets of x6_layout.h on this as one cyclic stream of chunks through a 4-slot
+// ring, each with a layer loop of its own (one loop for the three, xt_layer, was built and compiled: every kernel's register
+// allocation moved, profiles/x6t_layer_refactor.md) made of the pieces at the end of this file: the bias table, xt_wait, xt_barrier,
+// xt_refill, xt_copy_ahead, xt_rotate, xt_prologue.
+// Timing ablations of those three kernels (wrong results; tools/build_variant.sh): -DXT_ABL_NOBAR no per-chunk barrier, -DXT_ABL_NOREAD no
+// fragment reads behind the prologue's, -DXT_ABL_NODMA no copies behind the prologue's.
 #pragma once
 #include "common.h"
 #include "mlp_engine.h"
@@ -69,7 +76,7 @@ __device__ __forceinline__ void xt_copy_piece(int i, const f4* src_span, unsigne
 }
 // The same pieces issued IN ORDER i = 0, 1, 2, ... by one wave within a chunk (the x6t kernels place them in consecutive filler
 // positions): six issue slots per piece (three for the lane offset, M0, the hazard nop, the copy) were 12 % of a K = 256 chunk's slots
-// (-DSXT_NODMA: 4.50 -> 3.88 ms per 2^20 points).  Piece 0 derives the lane offset and sets M0, piece 4 advances both by 4 KB, every
+// (-DXT_ABL_NODMA: 4.50 -> 3.88 ms per 2^20 points).  Piece 0 derives the lane offset and sets M0, piece 4 advances both by 4 KB, every
 // other piece is ONE instruction: the offset register `lv` and M0 are carried from piece to piece.  Nothing else between the pieces of
 // a chunk may write M0: no other instruction of these kernels does (checked in the ISA; sdf_back_x6t's gate copies, which set M0,
 // are issued before piece 0).
@@ -177,6 +184,87 @@ __device__ __forceinline__ void xt_request(u4 (&dst)[4], unsigned slot_lane_addr
       const int k = down ? count - 1 - k_ : k_;
       dst[k] = base[((kb_first + k) * 3 + piece) * 64];
     }
+}
+
+// ---- pieces of the layer loops of sdf_x6t.hip, color_x6t.hip, sdf_back_x6t.hip.  The ring: four slots for the fragments of a chunk;
+// slot_b[i] = byte offset of the slot that holds chunk i (mod 4) of the CURRENT layer, ring_lane = the ring's LDS address + lane 16.
+
+// the 16 biases of every chunk of the stream, resident in the LDS
+template <class Stream>
+__device__ __forceinline__ void xt_load_bias(f4* bias_tab, const f4* W, int tid) {
+  for (int i = tid; i < Stream::nchunk() * 4; i += 256) bias_tab[i] = W[Stream::coff(i >> 2) + (i & 3)];
+}
+template <class Stream>
+__device__ __forceinline__ f4 xt_bias_of(const f4* bias_tab, int c, int g) {      // c = stream position (may run past the end once)
+  const int cc = c >= Stream::nchunk() ? c - Stream::nchunk() : c;
+  return bias_tab[cc * 4 + g];
+}
+// s_waitcnt vmcnt(n) for an n that the unrolled chunk loop folds to a constant
+__device__ __forceinline__ void xt_wait(int n) {
+  switch (n) {
+#define XT_W_(N) case N: sx_wait<N>(); break;
+    XT_W_(1) XT_W_(2) XT_W_(3) XT_W_(4) XT_W_(5) XT_W_(6) XT_W_(7) XT_W_(8) XT_W_(9) XT_W_(10) XT_W_(11) XT_W_(12)
+    XT_W_(13) XT_W_(14) XT_W_(15) XT_W_(16) XT_W_(17) XT_W_(18) XT_W_(19) XT_W_(20) XT_W_(21) XT_W_(22) XT_W_(23) XT_W_(24)
+#undef XT_W_
+    default: sx_wait<0>(); break;      // any count not listed: the strictest wait (safe)
+  }
+}
+// the barrier at the top of a chunk (behind the counted wait): chunk jb + 1 has landed in every wave's view, and every wave has finished
+// with chunk jb - 1, whose slot the copies of chunk jb + 3 reuse
+__device__ __forceinline__ void xt_barrier() {
+#ifndef XT_ABL_NOBAR
+  __builtin_amdgcn_s_barrier();
+#endif
+  asm volatile("" ::: "memory");
+}
+// xt_chunk's refill for chunk jb of a layer of NCH chunks of K: the next part's fragments of `piece` -- behind the chunk's last part
+// those of the next chunk's first part, from the next slot (KN: the K of the layer behind this one)
+template <int K, int KN, int NCH>
+__device__ __forceinline__ void xt_refill(XtWin& win, unsigned ring_lane, const unsigned (&slot_b)[4], int jb, int piece, int part) {
+  constexpr int WK = xt_wk(K), NPART = xt_parts(K), WKN = xt_wk(KN);
+  const bool down = ((jb * NPART + part) & 1) != 0;
+  int slot, kb_first, count;
+  if (part + 1 < NPART) {
+    slot = jb & 3, kb_first = (part + 1) * WK, count = WK;
+  } else {
+    slot = (jb + 1) & 3, kb_first = 0, count = jb + 1 < NCH ? WK : WKN;
+  }
+  u4(&d)[4] = piece == 0 ? win.h : (piece == 1 ? win.m : win.l);
+#ifdef XT_ABL_NOREAD                      // the registers are redefined behind the compiler's back (no instruction)
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < count) asm volatile("" : "+v"(d[k]));
+  (void)slot, (void)kb_first, (void)down;
+#else
+  xt_request(d, ring_lane + slot_b[slot], kb_first, count, piece, down);
+#endif
+}
+// piece i of this wave's copies of the chunk three ahead (xt_copy_piece_seq)
+__device__ __forceinline__ void xt_copy_ahead(int i, const f4* src_span, unsigned dst_span, unsigned& lv, bool have_lv = false) {
+#ifndef XT_ABL_NODMA
+  xt_copy_piece_seq(i, src_span, dst_span, lv, have_lv);
+#endif
+}
+template <int R>
+__device__ __forceinline__ void xt_rotate(unsigned (&slot_b)[4]) {      // slot 0 = the slot of chunk R: the next layer's first chunk
+  unsigned a[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = slot_b[(i + R) & 3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) slot_b[i] = a[i];
+}
+// chunks 0, 1, 2 of the stream (all of the first layer: K0) into slots 0, 1, 2 and the first fragment window; first0: xt_span_first(K0, wave)
+template <class Stream, int K0>
+__device__ __forceinline__ void xt_prologue(const f4* W, unsigned ring_b, unsigned ring_lane, const unsigned (&slot_b)[4], int first0, XtWin& win) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int i = 0; i < sx_nsw(K0); ++i) xt_copy_piece(i, W + Stream::coff(c) + 4 + first0 * 64, ring_b + slot_b[c] + (unsigned)first0 * 1024u);
+  sx_wait<0>();
+  __syncthreads();
+  xt_request(win.h, ring_lane + slot_b[0], 0, xt_wk(K0), 0, true);
+  xt_request(win.m, ring_lane + slot_b[0], 0, xt_wk(K0), 1, true);
+  xt_request(win.l, ring_lane + slot_b[0], 0, xt_wk(K0), 2, true);
 }
 
 }  // namespace rb

@@ -764,6 +764,41 @@ def test_color_exact_operand_kernel(dev, synth_weights):
     ops.range_check(sync=True)
 
 
+def test_two_tile_kernels_several_rounds_per_workgroup(dev, synth_weights):
+    """k_sdf_x6t<0,1> and k_color_x6t (csrc/sdf_x6t.hip, color_x6t.hip) with 1, 2 and 3 persistent workgroups at 1000 rows -- eight
+    rounds of 128, the last one ragged, so a workgroup walks the ring across rounds (and sdf_x6t finishes a round's last chunk beside
+    the next round's layer 0) -- bit for bit what the default grid (one round per workgroup here) gives."""
+    import ctypes
+    from robir_amd import _lib, packing
+    L, n = _lib.lib(), 1000
+    g = torch.Generator().manual_seed(131)
+    x = ((torch.rand(n, 3, generator=g) - 0.5) * 0.6).to(dev)
+    v = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).to(dev)
+    nr = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).to(dev)
+    feat = torch.randn(n, 257, generator=g).to(dev)
+    col6 = packing.pack_color_x6(synth_weights, dev)
+
+    def sdf(mode, blob, wgs):
+        out = torch.full((n, 257) if mode else (n,), float("nan"), device=dev)
+        assert L.rb_sdf_x6_points(_lib.ptr(x), ctypes.c_long(n), ctypes.c_float(1.0), _lib.ptr(blob), ctypes.c_int(mode), ctypes.c_float(1.0),
+                                  _lib.ptr(out), ctypes.c_int(1), ctypes.c_int(wgs), _lib.stream_ptr()) == 0, L.rb_last_error()
+        return out
+
+    def color(wgs):
+        rgb = torch.full((n, 3), float("nan"), device=dev)
+        assert L.rb_color_x6_points(ctypes.c_void_p(feat[:, 1:].data_ptr()), ctypes.c_long(feat.stride(0)), ctypes.c_float(1.0), _lib.ptr(x),
+                                    ctypes.c_float(1.0), _lib.ptr(v), _lib.ptr(nr), ctypes.c_long(n), _lib.ptr(col6), _lib.ptr(rgb),
+                                    ctypes.c_int(1), ctypes.c_int(wgs), _lib.stream_ptr()) == 0, L.rb_last_error()
+        return rgb
+
+    for name, run in (("distance", lambda w, b=packing.pack_sdf_x6(synth_weights, dev, full=False): sdf(0, b, w)),
+                      ("all outputs", lambda w, b=packing.pack_sdf_x6(synth_weights, dev, full=True): sdf(1, b, w)), ("colour", color)):
+        ref = run(0)
+        assert bool(torch.isfinite(ref).all()), name
+        for wgs in (1, 2, 3):
+            assert torch.equal(run(wgs), ref), (name, wgs)
+
+
 def test_vis_exact_operand_kernel(dev, synth_weights):
     """k_vis_x6 (csrc/vis_x6.hip) against the f32-input-MFMA visibility MLP on the same points and directions: ragged sizes, several
     directions per point, many rounds, run to run."""

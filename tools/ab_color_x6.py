@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Timing and agreement of the two forms of the exact-operand colour kernel (csrc/color_x6.hip: one tile per wave, color_x6t.hip: two):
-`python tools/ab_color_x6.py [rows ...]`."""
+`python tools/ab_color_x6.py [rows ...]` (the library: ROBIR_AB_LIB, else the shipped one; the two-tile form's timing ablations are
+csrc/x6t_engine.h's -DXT_ABL_NOBAR / _NOREAD / _NODMA and color_x6t.hip's -DCT_ABL_NOEP / _LOAD_ONCE: wrong results on purpose)."""
 import os
 import sys
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Timing of the exact-operand SDF kernels of one library build: `python tools/ab_sdf_x6.py [<tag> [<lib.so>]]` (the library: the argument, else ROBIR_AB_LIB, else the shipped one; A/B and ablation builds
-made by tools/build_variant.sh; the engine's -DSX_ABL_NOBAR / _NOREAD / _NODMA (csrc/x6_ring.h) and the SDF epilogue's -DSXA_NOEPI give
-wrong results on purpose)."""
+made by tools/build_variant.sh; the engines' -DSX_ABL_NOBAR / _NOREAD / _NODMA (one tile per wave: csrc/x6_ring.h) and -DXT_ABL_NOBAR / _NOREAD /
+_NODMA (two tiles: csrc/x6t_engine.h) and the SDF epilogue's -DSXA_NOEPI give wrong results on purpose)."""
 import os
 import sys
 
