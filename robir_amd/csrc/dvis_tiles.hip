@@ -1,21 +1,13 @@
 // The two passes around the persistent tile-list ("stream") form of the light-visibility kernels -- k_dvis_x6t<stream>
-// (vis_diffuse_x6t.hip), k_dvis_f16t (vis_diffuse_f16t.hip) and the legacy k_dvis3_stream (vis_diffuse_v3.hip, where they came from):
+// (vis_diffuse_x6t.hip), k_dvis_f16t / k_dvis_f16t2 (vis_diffuse_f16t.hip) and the legacy k_dvis3_stream (vis_diffuse_v3.hip); dvis_tiles.h
+// has the tile record, their prototypes and the host side of a launch:
 //   k_dvis3_cull    one workgroup per point: cull n.d <= 1e-6 (model/sg_render.py:155), compact the surviving direction indices into a
 //                   GLOBAL list of 16-sample tiles (wave ballot + prefix count, one atomic per point for its tile range);
 //   k_dvis3_reduce  one workgroup per point: scatter its pair values by direction index, SG-weighted mean per lobe in the fixed sample
 //                   order (sg_render.py:177-190).
-#include "../../include/robir_hip.h"
-#include "common.h"
+#include "dvis_tiles.h"
 
 namespace rb {
-
-#define RB_TINY 1e-6f
-constexpr int V3_MAX_DIRS = 4096;
-
-struct V3Tile {
-  int point;       // -1: no such tile
-  int dir_base;    // first row of the point's chunk in dirs / Bd (chunk id * L * nsamp)
-};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // cull + compaction: one workgroup per point
@@ -23,10 +15,10 @@ struct V3Tile {
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_dvis3_cull(const float* __restrict__ normals, const int* __restrict__ cid, long n,
                                                      const float* __restrict__ dirs, int LS, unsigned short* __restrict__ pair_j,
-                                                     V3Tile* __restrict__ tile_info, int2* __restrict__ point_info,
+                                                     DvisTile* __restrict__ tile_info, int2* __restrict__ point_info,
                                                      unsigned long long* __restrict__ counters,
                                                      unsigned long long* __restrict__ eval_count) {
-  __shared__ unsigned short idx_list[V3_MAX_DIRS];
+  __shared__ unsigned short idx_list[DVIS_MAX_DIRS];
   __shared__ int s_count, s_tile0;
   const int tid = threadIdx.x, lane = tid & 63;
   const long p = blockIdx.x;
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(256) void k_dvis3_cull(const float* __restrict__ no
   const int t0 = s_tile0;
   if (tid == 0) point_info[p] = make_int2(t0, S);
   for (int i = tid; i < nt * 16; i += 256) pair_j[(long)t0 * 16 + i] = i < S ? idx_list[i] : (unsigned short)0xFFFF;
-  for (int i = tid; i < nt; i += 256) tile_info[t0 + i] = V3Tile{(int)p, dbase};
+  for (int i = tid; i < nt; i += 256) tile_info[t0 + i] = DvisTile{(int)p, dbase};
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(256) void k_dvis3_reduce(const int* __restrict__ ci
                                                        const float* __restrict__ wsum, const unsigned short* __restrict__ pair_j,
                                                        const float* __restrict__ pair_vis, const int2* __restrict__ point_info,
                                                        int L, int nsamp, float* __restrict__ vis_out) {
-  __shared__ float vis_tab[V3_MAX_DIRS];
+  __shared__ float vis_tab[DVIS_MAX_DIRS];
   const int tid = threadIdx.x;
   const long p = blockIdx.x;
   const int LS = L * nsamp;

@@ -9,13 +9,11 @@
 //     128 survivors (4 waves x 2 tiles x 16) through the three 256x256 hidden layers on the fp32 MFMA engine
 //     (mlp_engine.h; activations stay in registers), VALU 256->2 head, softmax, result scattered to an LDS
 //     visibility table; finally the SG-weighted mean per lobe (deterministic order).
-#include "../../include/robir_hip.h"
-#include "common.h"
+#include "dvis_tiles.h"
 #include "mlp_engine.h"
 
 namespace rb {
 
-#define RB_TINY 1e-6f
 
 __device__ __forceinline__ void unit_eps(float v[3]) {  // norm_axis (sg_render.py:107-108)
   float n = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) + RB_TINY;
@@ -76,7 +74,6 @@ __global__ void k_dvis_dirs(const float* __restrict__ lgt, int L, int nsamp, int
   wsum[i] = s + RB_TINY;
 }
 
-constexpr int DV_MAX_DIRS = 4096;
 
 template <bool H3, int CH, int NT, bool DMA = false>
 __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void k_dvis_fused(
@@ -87,8 +84,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void k_dvis_fused(
     unsigned long long* __restrict__ eval_count, unsigned* __restrict__ range_word) {
   unsigned sat = 0u;   // range sentinel of the split-precision path (operands are ReLU outputs: >= 0)
   __shared__ f4 lds_w[(H3 ? 3 : 2) * chunk_f4(256)];
-  __shared__ float vis_tab[DV_MAX_DIRS];
-  __shared__ unsigned short idx_list[DV_MAX_DIRS];
+  __shared__ float vis_tab[DVIS_MAX_DIRS];
+  __shared__ unsigned short idx_list[DVIS_MAX_DIRS];
   __shared__ f4 a_row[64];
   __shared__ f4 w_last[128];  // [2][256]
   __shared__ int s_count;
@@ -224,17 +221,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void k_dvis_fused(
       l1 += __shfl_xor(l1, 32);
       l0 += b0;
       l1 += b1;
-      if (g == 0 && jj[t] >= 0) {
-        float v;
-        if (argmax_vis) {
-          v = l1 > l0 ? 1.f : 0.f;
-        } else {
-          const float mx = fmaxf(l0, l1);
-          const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-          v = e1 / (e0 + e1);
-        }
-        vis_tab[jj[t]] = v;
-      }
+      if (g == 0 && jj[t] >= 0) vis_tab[jj[t]] = dvis_value(l0, l1, argmax_vis);
     }
   }
   if constexpr (H3) range_report<true>(sat, range_word);
@@ -272,7 +259,7 @@ int rb_dvis_fused(const float* normals, const int* chunk_id, long n, const float
   RB_REQUIRE(precision == 0 || precision == 5, "precision: 0 = fp32 MFMA; 5 = f16x3 split (first-generation kernel)");
   RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && Whid && wlast && blast && vis_out, "null pointer");
   RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DV_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
+  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DVIS_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
   if (precision == 0) {
     hipLaunchKernelGGL((k_dvis_fused<false, 1, 2>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, normals, chunk_id, n, A,
                        Bd, dirs, wdir, wsum, (const f4*)Whid, wlast, blast, L, nsamp, argmax_vis, 1.0f, vis_out, eval_count,

@@ -13,15 +13,12 @@
 //   * the relu + hi/lo split of a chunk's result runs under the next chunk's MFMAs and writes straight into the next
 //     layer's operand registers (no fp32 copy of the layer output);
 //   * the 256->2 head is a 49th, LDS-resident chunk on the matrix pipe.
-#include "../../include/robir_hip.h"
-#include "common.h"
+#include "dvis_tiles.h"
 #include "mlp_engine.h"
 #include <cstdlib>
 
 namespace rb {
 
-#define RB_TINY 1e-6f
-constexpr int V2_MAX_DIRS = 4096;
 constexpr int V2_CF4 = chunk_f4(256);   // float4s per packed chunk in global memory (bias + weights)
 constexpr int V2_WF4 = 1024;            // weight part of a chunk (16 KB)
 constexpr int V2_SLOTS = 4, V2_DIST = 3;
@@ -67,8 +64,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_v2(
   __shared__ f4 ring[V2_SLOTS * V2_WF4];   // 64 KB
   __shared__ f4 headw[V2_WF4];             // 16 KB: chunk 48 (256 -> 2 head, rows 2..15 zero)
   __shared__ f4 bias_tab[49 * 4];
-  __shared__ float vis_tab[V2_MAX_DIRS];
-  __shared__ unsigned short idx_list[V2_MAX_DIRS];
+  __shared__ float vis_tab[DVIS_MAX_DIRS];
+  __shared__ unsigned short idx_list[DVIS_MAX_DIRS];
   __shared__ f4 a_row[64];
   __shared__ int s_count;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
@@ -296,17 +293,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_v2(
         f4 r = acc.a[t][0];
         if constexpr (V2_CH == 2) r = r + acc.a[t][1];
         const float l0 = r[0] * w_unscale, l1 = r[1] * w_unscale;
-        if (g == 0 && jj[t] >= 0) {
-          float v;
-          if (argmax_vis) {
-            v = l1 > l0 ? 1.f : 0.f;
-          } else {
-            const float mx = fmaxf(l0, l1);
-            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-            v = e1 / (e0 + e1);
-          }
-          vis_tab[jj[t]] = v;
-        }
+        if (g == 0 && jj[t] >= 0) vis_tab[jj[t]] = dvis_value(l0, l1, argmax_vis);
       }
     }
     V2_T(4)
@@ -339,7 +326,7 @@ extern "C" int rb_dvis_fused_v2(const float* normals, const int* chunk_id, long 
   if (n <= 0) return 0;
   RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
   RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= V2_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
+  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DVIS_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
   // RB_V2_TIMED=1: per-phase shader-clock totals (rb_dvis_v2_debug), a profiling aid -- costs ~10 % in the kernel
   static const char* const tm = getenv("RB_V2_TIMED");   // read once
 #define RB_V2(T)                                                                                                          \

@@ -18,32 +18,17 @@
 // number of points -- a single 1024-pixel chunk (~660 points) filled 2.6 waves of one-point workgroups before; (3) no
 // host-visible sizes anywhere: the grid is fixed, the tile count is read from device memory, so the caller never
 // synchronises.
-#include "../../include/robir_hip.h"
-#include "common.h"
+// k_dvis3_cull / k_dvis3_reduce, the tile record and the host side of a launch are shared with the exact-operand and f16 forms of the
+// default library: dvis_tiles.h / dvis_tiles.hip (round 5: this file is legacy-only).
+#include "dvis_tiles.h"
 #include "mlp_engine.h"
 #include <cstdlib>
 
 namespace rb {
 
-#define RB_TINY 1e-6f
-constexpr int V3_MAX_DIRS = 4096;
 constexpr int V3_CF4 = chunk_f4(256);   // float4s per packed chunk in global memory (bias + weights)
 constexpr int V3_WF4 = 1024;            // weight part of a chunk (16 KB)
 constexpr int V3_SLOTS = 4, V3_DIST = 3;
-
-struct V3Tile {
-  int point;       // -1: no such tile
-  int dir_base;    // first row of the point's chunk in dirs / Bd (chunk id * L * nsamp)
-};
-
-// k_dvis3_cull / k_dvis3_reduce: the passes around the persistent tile-list kernel, shared with the exact-operand and f16 forms of the
-// default library -- defined in dvis_tiles.hip (round 5: this file is legacy-only)
-__global__ void k_dvis3_cull(const float* __restrict__ normals, const int* __restrict__ cid, long n, const float* __restrict__ dirs, int LS,
-                             unsigned short* __restrict__ pair_j, V3Tile* __restrict__ tile_info, int2* __restrict__ point_info,
-                             unsigned long long* __restrict__ counters, unsigned long long* __restrict__ eval_count);
-__global__ void k_dvis3_reduce(const int* __restrict__ cid, long n, const float* __restrict__ wdir, const float* __restrict__ wsum,
-                               const unsigned short* __restrict__ pair_j, const float* __restrict__ pair_vis,
-                               const int2* __restrict__ point_info, int L, int nsamp, float* __restrict__ vis_out);
 
 // global -> LDS copy of 16 B per lane: wave-uniform LDS base in M0, uniform global base + per-lane byte offset
 __device__ __forceinline__ void v3_dma16(const f4* gbase_uniform, unsigned lane_byte_off, unsigned lds_byte_uniform) {
@@ -71,7 +56,7 @@ struct V3Acc {
 template <bool SENT>
 __global__ __launch_bounds__(256, 1) void k_dvis3_stream(
     const float* __restrict__ A, const float* __restrict__ Bd, const f4* __restrict__ W49,
-    const unsigned short* __restrict__ pair_j, const V3Tile* __restrict__ tile_info,
+    const unsigned short* __restrict__ pair_j, const DvisTile* __restrict__ tile_info,
     const unsigned long long* __restrict__ counters, int argmax_vis, float w_unscale, float* __restrict__ pair_vis,
     unsigned* __restrict__ range_word) {
   __shared__ f4 ring[V3_SLOTS * V3_WF4];   // 64 KB
@@ -109,7 +94,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis3_stream(
   int jraw2[2];            // ... in the round after next
   auto tile_rec = [&](long round, int t, int& pt, int& base) {
     const long T = round * 8 + wave * 2 + t;
-    V3Tile rec{-1, 0};
+    DvisTile rec{-1, 0};
     if (round < total_rounds && T < total_tiles) rec = tile_info[T];   // wave-uniform address: scalar load
     pt = __builtin_amdgcn_readfirstlane(rec.point);
     base = __builtin_amdgcn_readfirstlane(rec.dir_base);
@@ -303,17 +288,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis3_stream(
       for (int t = 0; t < 2; ++t) {
         const f4 r = acc.a[t];
         const float l0 = r[0] * w_unscale, l1 = r[1] * w_unscale;
-        if (g == 0 && jj[t] >= 0) {
-          float v;
-          if (argmax_vis) {
-            v = l1 > l0 ? 1.f : 0.f;
-          } else {
-            const float mx = fmaxf(l0, l1);
-            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-            v = e1 / (e0 + e1);
-          }
-          pair_vis[(rd * 8 + wave * 2 + t) * 16 + (lane & 15)] = v;
-        }
+        if (g == 0 && jj[t] >= 0) pair_vis[(rd * 8 + wave * 2 + t) * 16 + (lane & 15)] = dvis_value(l0, l1, argmax_vis);
       }
     }
     parity ^= 1;
@@ -333,40 +308,13 @@ extern "C" int rb_dvis_stream(const float* normals, const int* chunk_id, long n,
                               int argmax_vis, int scale_log2, unsigned short* pair_j, float* pair_vis, int* tile_info,
                               int* point_info, unsigned long long* counters, int n_workgroups, float* vis_out,
                               unsigned long long* eval_count, rb_stream_t stream) {
-  if (n <= 0) return 0;
-  RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
-  RB_REQUIRE(pair_j && pair_vis && tile_info && point_info && counters, "null scratch pointer");
-  RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each in the cull / reduce passes)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= V3_MAX_DIRS && (L * nsamp) % 16 == 0,
-             "need L <= 256, L*nsamp <= 4096 and a multiple of 16");
-  RB_REQUIRE((long)n * (L * nsamp / 16) < (1L << 31), "tile index would overflow 31 bits");
-  hipStream_t s = (hipStream_t)stream;
-  if (n_workgroups <= 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return rb::fail(__func__, "device query failed");
-      cus = prop.multiProcessorCount;
-    }
-    n_workgroups = cus;
-  }
-  if (hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return rb::fail(__func__, "memset failed");
-  hipLaunchKernelGGL(k_dvis3_cull, dim3((unsigned)n), dim3(256), 0, s, normals, chunk_id, n, dirs, L * nsamp, pair_j,
-                     reinterpret_cast<V3Tile*>(tile_info), reinterpret_cast<int2*>(point_info), counters, eval_count);
-  if (int rc = check_launch("k_dvis3_cull")) return rc;
-  static const char* const nosent = getenv("RB_V3_NO_SENTINEL");   // A/B switch for measuring the sentinel's cost
-  const float us = ldexpf(1.0f, -scale_log2);
-  unsigned* rw = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
-  if (nosent && nosent[0] == '1') {
-    hipLaunchKernelGGL(k_dvis3_stream<false>, dim3((unsigned)n_workgroups), dim3(256), 0, s, A, Bd, (const f4*)W49, pair_j,
-                       reinterpret_cast<const V3Tile*>(tile_info), counters, argmax_vis, us, pair_vis, rw);
-  } else {
-    hipLaunchKernelGGL(k_dvis3_stream<true>, dim3((unsigned)n_workgroups), dim3(256), 0, s, A, Bd, (const f4*)W49, pair_j,
-                       reinterpret_cast<const V3Tile*>(tile_info), counters, argmax_vis, us, pair_vis, rw);
-  }
-  if (int rc = check_launch("k_dvis3_stream")) return rc;
-  hipLaunchKernelGGL(k_dvis3_reduce, dim3((unsigned)n), dim3(256), 0, s, chunk_id, n, wdir, wsum, pair_j, pair_vis,
-                     reinterpret_cast<const int2*>(point_info), L, nsamp, vis_out);
-  return check_launch("k_dvis3_reduce");
+  return dvis_tile_list_launch(
+      __func__, nullptr, "k_dvis3_stream", normals, chunk_id, n, A, Bd, dirs, wdir, wsum, W49, L, nsamp, pair_j, pair_vis, tile_info, point_info,
+      counters, n_workgroups, vis_out, eval_count, stream, [&](const DvisTile* tiles, dim3 grid, hipStream_t s) {
+        static const char* const nosent = getenv("RB_V3_NO_SENTINEL");   // A/B switch for measuring the sentinel's cost
+        const float us = ldexpf(1.0f, -scale_log2);
+        unsigned* rw = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
+        auto* const kernel = nosent && nosent[0] == '1' ? k_dvis3_stream<false> : k_dvis3_stream<true>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, A, Bd, (const f4*)W49, pair_j, tiles, counters, argmax_vis, us, pair_vis, rw);
+      });
 }

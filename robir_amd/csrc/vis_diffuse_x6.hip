@@ -21,14 +21,11 @@
 // between the MFMAs of the current one, the 256 -> 2 head as a 49th LDS-resident chunk.  A chunk's 48 MFMAs are issued as
 // six runs of eight on one accumulator each (wl.xh, wm.xm, wh.xl | wm.xh, wh.xm | wh.xh): a weight piece's registers are
 // refilled with the next chunk's as soon as its last run has issued.
-#include "../../include/robir_hip.h"
-#include "common.h"
+#include "dvis_tiles.h"
 #include "mlp_engine.h"
 
 namespace rb {
 
-#define RB_TINY 1e-6f
-constexpr int X6_MAX_DIRS = 4096;
 constexpr int X6_WF4 = 1536;             // weight part of a packed chunk: [kb 8][piece 3][lane 64] x 16 B = 24 KB
 constexpr int X6_CF4 = 4 + X6_WF4;       // packed chunk in global memory: 16 bias floats + weights
 constexpr int X6_SLOTS = 4, X6_DIST = 3;
@@ -79,8 +76,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6(
   __shared__ f4 ring[X6_SLOTS * X6_WF4];   // 96 KB
   __shared__ f4 headw[X6_WF4];             // 24 KB: chunk 48 (256 -> 2 head, rows 2..15 zero)
   __shared__ f4 bias_tab[49 * 4];
-  __shared__ float vis_tab[X6_MAX_DIRS];
-  __shared__ unsigned short idx_list[X6_MAX_DIRS];
+  __shared__ float vis_tab[DVIS_MAX_DIRS];
+  __shared__ unsigned short idx_list[DVIS_MAX_DIRS];
   __shared__ f4 a_row[64];
   __shared__ int s_count;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
@@ -366,17 +363,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6(
       bias = bias_tab[g];
       const float l0 = __builtin_fmaf(__builtin_fmaf(acc.c2[0], C11, acc.c1[0]), C11, acc.c0[0]) * w_unscale;
       const float l1 = __builtin_fmaf(__builtin_fmaf(acc.c2[1], C11, acc.c1[1]), C11, acc.c0[1]) * w_unscale;
-      if (g == 0 && jj >= 0) {
-        float v;
-        if (argmax_vis) {
-          v = l1 > l0 ? 1.f : 0.f;
-        } else {
-          const float mx = fmaxf(l0, l1);
-          const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-          v = e1 / (e0 + e1);
-        }
-        vis_tab[jj] = v;
-      }
+      if (g == 0 && jj >= 0) vis_tab[jj] = dvis_value(l0, l1, argmax_vis);
     }
   }
 #undef X6_MFMA
@@ -403,7 +390,7 @@ extern "C" int rb_dvis_fused_x6(const float* normals, const int* chunk_id, long 
   if (n <= 0) return 0;
   RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
   RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= X6_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
+  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DVIS_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
 #if !X6_UNSCALE
   RB_REQUIRE(scale_log2 == 0, "this build of k_dvis_x6 takes weights packed with scale_log2 = 0");
 #endif

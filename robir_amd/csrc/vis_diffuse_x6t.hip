@@ -21,18 +21,16 @@
 // drained between points: the stream of chunk copies that a point's last layer continues into "the next round" IS the next point's
 // first round.  eval_count is summed per workgroup and added once; the range sentinel is reported once.  Outputs are bit-identical
 // to one workgroup per point (the same instructions per pair; only the order of points on a compute unit differs).
-#include "../../include/robir_hip.h"
-#include "common.h"
+#include "dvis_tiles.h"
 #include "mlp_engine.h"
 #include "x6_ring.h"
+#include "x6t_engine.h"
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
 
 namespace rb {
 
-#define RB_TINY 1e-6f
-constexpr int XT_MAX_DIRS = 4096;
 constexpr int XT_WF4 = 1536;             // weight part of a packed chunk: [kb 8][piece 3][lane 64] x 16 B = 24 KB
 constexpr int XT_CF4 = 4 + XT_WF4;       // packed chunk in global memory: 16 bias floats + weights
 constexpr int XT_SLOTS = 4, XT_DIST = 3;
@@ -60,23 +58,8 @@ __device__ __forceinline__ void xt_dma16(const f4* gbase_uniform, unsigned lane_
                "s"(gbase_uniform)
                : "memory");
 }
-// ... with an immediate offset, which advances the global AND the LDS address (x6_ring.h: sx_dma_block)
-template <int OFF>
-__device__ __forceinline__ void xt_dma16_imm(const f4* gbase_uniform, unsigned lane_byte_off, unsigned lds_byte_uniform) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(lds_byte_uniform), "v"(lane_byte_off),
-               "s"(gbase_uniform), "n"(OFF)
-               : "memory");
-}
+// (with an immediate offset, and with M0 kept from the copy before: xt_dma16_imm / xt_dma16_keep of x6t_engine.h)
 
-template <int OFF>
-__device__ __forceinline__ void xt_dma16_m0kept(const f4* gbase_uniform, unsigned lane_byte_off) {
-  asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" ::"v"(lane_byte_off), "s"(gbase_uniform), "n"(OFF) : "memory");
-}
-
-struct XtTile {     // = V3Tile (vis_diffuse_v3.hip): record of a 16-sample tile of the global list
-  int point;        // -1: no such tile
-  int dir_base;     // first row of the point's chunk in dirs / Bd (chunk id * L * nsamp)
-};
 struct XtArgs {
   // both forms
   const float *A, *Bd;
@@ -91,9 +74,9 @@ struct XtArgs {
   unsigned long long* eval_count;
   long n;
   unsigned* queue;      // the next point to hand out (zeroed in front of the launch)
-  // persistent grid over the global tile list (STREAM = true; k_dvis3_cull / k_dvis3_reduce of vis_diffuse_v3.hip around it)
+  // persistent grid over the global tile list (STREAM = true; k_dvis3_cull / k_dvis3_reduce of dvis_tiles.hip around it)
   const unsigned short* pair_j;
-  const XtTile* tile_info;
+  const DvisTile* tile_info;
   const unsigned long long* counters;
   float* pair_vis;
 };
@@ -118,12 +101,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   __shared__ f4 headw[XT_WF4];             // 24 KB: chunk 48 (256 -> 2 head, rows 2..15 zero)
   __shared__ f4 bias_tab[49 * 4];
   // per point: vis_tab[4096] float | idx_list[4096] u16 | a_row[64] f4 = 25 KB; stream: a_rows [round parity][tile of the round][64] f4 = 16 KB
-  __shared__ f4 aux[(XT_MAX_DIRS * 4 + XT_MAX_DIRS * 2) / 16 + 64];
+  __shared__ f4 aux[(DVIS_MAX_DIRS * 4 + DVIS_MAX_DIRS * 2) / 16 + 64];
   __shared__ int s_count;
   __shared__ unsigned s_next;              // per-point form: the point lane 0 took from the queue
   float* const vis_tab = reinterpret_cast<float*>(aux);
-  unsigned short* const idx_list = reinterpret_cast<unsigned short*>(aux + XT_MAX_DIRS / 4);
-  f4* const a_row = aux + (XT_MAX_DIRS * 6) / 16;
+  unsigned short* const idx_list = reinterpret_cast<unsigned short*>(aux + DVIS_MAX_DIRS / 4);
+  f4* const a_row = aux + (DVIS_MAX_DIRS * 6) / 16;
   f4* const a_rows = aux;
   const float* __restrict__ A = a.A;
   const float* __restrict__ Bd = a.Bd;
@@ -164,10 +147,9 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   // fragment (kb, piece) of a slot: ring_u[slot * XT_WF4 + (kb * 3 + piece) * 64].  Two base registers (slots 0, 1 | 2, 3) keep every
   // read's offset inside the 16-bit immediate of ds_read_b128 (the ring is 96 KB: from one base the compiler keeps an address
   // register per fragment, parked in the accumulator file and fetched back before every read)
-  typedef const __attribute__((address_space(3))) u4* lds_u4p;
   unsigned ring_a0 = ring_b + (unsigned)lane * 16u, ring_a2 = ring_a0 + 2u * XT_WF4 * 16u;
   asm volatile("" : "+v"(ring_a0), "+v"(ring_a2));
-  const lds_u4p ring_u = (lds_u4p)ring_a0, ring_u2 = (lds_u4p)ring_a2;
+  const xt_lds_u4p ring_u = (xt_lds_u4p)ring_a0, ring_u2 = (xt_lds_u4p)ring_a2;
   u4 wh[4], wm[4], wl[4];              // rolling window: the fragments of four k-blocks (half a chunk)
 #if XT_FP8
   typedef int xt_i8 __attribute__((ext_vector_type(8)));
@@ -292,7 +274,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   const unsigned arow_b = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)a_rows);
   // (branch-free: a conditional load makes the compiler wait for the record at the join, i.e. at the top of the round; loaded
   // unconditionally from a clamped index the record is waited for where the head uses it, a round later)
-  XtTile recn[2] = {{-1, 0}, {-1, 0}};
+  DvisTile recn[2] = {{-1, 0}, {-1, 0}};
   bool okn[2] = {false, false};
   auto tile_lookup = [&](long round) {
 #pragma unroll
@@ -495,9 +477,9 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #define XT_COPY(I)                                                                  \
   do {                                                                              \
     if ((I) == 0) xt_dma16_imm<0>(dsrc, voff_a, ddst);                              \
-    else if ((I) < 4) xt_dma16_m0kept<((I) & 3) * 1024>(dsrc, voff_a);              \
+    else if ((I) < 4) xt_dma16_keep<((I) & 3) * 1024>(dsrc, voff_a);              \
     else if ((I) == 4) xt_dma16_imm<0>(dsrc, voff_b, ddst + 4096u);                 \
-    else xt_dma16_m0kept<((I) & 3) * 1024>(dsrc, voff_b);                           \
+    else xt_dma16_keep<((I) & 3) * 1024>(dsrc, voff_b);                           \
   } while (0)
 #endif
 #define XT_FENCE __builtin_amdgcn_sched_barrier(0)
@@ -533,7 +515,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #pragma unroll
         for (int H = 0; H < 2; ++H) {
           // the next half's fragments: second half of this chunk's slot | first half of the next chunk's
-          const lds_u4p nfrag = (((jb + H) & 2) ? ring_u2 : ring_u) + ((jb + H) & 1) * XT_WF4;
+          const xt_lds_u4p nfrag = (((jb + H) & 2) ? ring_u2 : ring_u) + ((jb + H) & 1) * XT_WF4;
           if (H == 0) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -736,14 +718,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         const float l0 = __builtin_fmaf(__builtin_fmaf(acc[t].c2[0], C11, acc[t].c1[0]), C11, acc[t].c0[0]);
         const float l1 = __builtin_fmaf(__builtin_fmaf(acc[t].c2[1], C11, acc[t].c1[1]), C11, acc[t].c0[1]);
         if (g == 0 && jj[t] >= 0) {
-          float v;
-          if (argmax_vis) {
-            v = l1 > l0 ? 1.f : 0.f;
-          } else {
-            const float mx = fmaxf(l0, l1);
-            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-            v = e1 / (e0 + e1);
-          }
+          const float v = dvis_value(l0, l1, argmax_vis);
           if constexpr (STREAM) a.pair_vis[(rd * 8 + wave * 2 + t) * 16 + (lane & 15)] = v;
           else vis_tab[jj[t]] = v;
         }
@@ -808,15 +783,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   __syncthreads();
 }
 
-// the cull / per-lobe reduce passes around the stream form: precision-agnostic (dvis_tiles.hip), shared with the legacy split-precision family
-struct V3Tile;
-__global__ void k_dvis3_cull(const float* __restrict__ normals, const int* __restrict__ cid, long n, const float* __restrict__ dirs, int LS,
-                             unsigned short* __restrict__ pair_j, V3Tile* __restrict__ tile_info, int2* __restrict__ point_info,
-                             unsigned long long* __restrict__ counters, unsigned long long* __restrict__ eval_count);
-__global__ void k_dvis3_reduce(const int* __restrict__ cid, long n, const float* __restrict__ wdir, const float* __restrict__ wsum,
-                               const unsigned short* __restrict__ pair_j, const float* __restrict__ pair_vis,
-                               const int2* __restrict__ point_info, int L, int nsamp, float* __restrict__ vis_out);
-
 }  // namespace rb
 
 using namespace rb;
@@ -859,7 +825,7 @@ extern "C" int rb_dvis_fused_x6t(const float* normals, const int* chunk_id, long
   if (n <= 0) return 0;
   RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
   RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= XT_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
+  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DVIS_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
 #if XT_FP8
   RB_REQUIRE(scale_log2 == 8, "this build of k_dvis_x6t takes the bf8 weight layout (packing.repack_x6_chunks_fp8; scale_log2 = 8 names it)");
 #else
@@ -884,32 +850,19 @@ extern "C" int rb_dvis_stream_x6(const float* normals, const int* chunk_id, long
                                  int argmax_vis, int scale_log2, unsigned short* pair_j, float* pair_vis, int* tile_info,
                                  int* point_info, unsigned long long* counters, int n_workgroups, float* vis_out,
                                  unsigned long long* eval_count, rb_stream_t stream) {
-  if (n <= 0) return 0;
-  RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
-  RB_REQUIRE(pair_j && pair_vis && tile_info && point_info && counters, "null scratch pointer");
-  RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each in the cull / reduce passes)");
-  RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= XT_MAX_DIRS && (L * nsamp) % 16 == 0,
-             "need L <= 256, L*nsamp <= 4096 and a multiple of 16");
-  RB_REQUIRE((long)n * (L * nsamp / 16) < (1L << 31), "tile index would overflow 31 bits");
 #if XT_FP8
-  RB_REQUIRE(scale_log2 == 8, "this build of k_dvis_x6t takes the bf8 weight layout (packing.repack_x6_chunks_fp8; scale_log2 = 8 names it)");
+  const char* const format_error =
+      scale_log2 == 8 ? nullptr : "this build of k_dvis_x6t takes the bf8 weight layout (packing.repack_x6_chunks_fp8; scale_log2 = 8 names it)";
 #else
-  RB_REQUIRE(scale_log2 == 0, "k_dvis_x6t takes weights packed with scale_log2 = 0");
+  const char* const format_error = scale_log2 == 0 ? nullptr : "k_dvis_x6t takes weights packed with scale_log2 = 0";
 #endif
-  hipStream_t s = (hipStream_t)stream;
-  if (n_workgroups <= 0) n_workgroups = device_cus();
-  RB_REQUIRE(n_workgroups > 0, "device query failed");
-  if (hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return rb::fail(__func__, "memset failed");
-  hipLaunchKernelGGL(k_dvis3_cull, dim3((unsigned)n), dim3(256), 0, s, normals, chunk_id, n, dirs, L * nsamp, pair_j,
-                     reinterpret_cast<V3Tile*>(tile_info), reinterpret_cast<int2*>(point_info), counters, eval_count);
-  if (int rc = check_launch("k_dvis3_cull")) return rc;
-  XtArgs a{};
-  a.A = A, a.Bd = Bd, a.W49 = (const f4*)W49, a.argmax_vis = argmax_vis;
-  a.range_word = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
-  a.pair_j = pair_j, a.tile_info = reinterpret_cast<const XtTile*>(tile_info), a.counters = counters, a.pair_vis = pair_vis;
-  hipLaunchKernelGGL(k_dvis_x6t<true>, dim3((unsigned)n_workgroups), dim3(256), 0, s, a);
-  if (int rc = check_launch("k_dvis_x6t<stream>")) return rc;
-  hipLaunchKernelGGL(k_dvis3_reduce, dim3((unsigned)n), dim3(256), 0, s, chunk_id, n, wdir, wsum, pair_j, pair_vis,
-                     reinterpret_cast<const int2*>(point_info), L, nsamp, vis_out);
-  return check_launch("k_dvis3_reduce");
+  return dvis_tile_list_launch(__func__, format_error, "k_dvis_x6t<stream>", normals, chunk_id, n, A, Bd, dirs, wdir, wsum, W49, L, nsamp, pair_j,
+                               pair_vis, tile_info, point_info, counters, n_workgroups, vis_out, eval_count, stream,
+                               [&](const DvisTile* tiles, dim3 grid, hipStream_t s) {
+                                 XtArgs a{};
+                                 a.A = A, a.Bd = Bd, a.W49 = (const f4*)W49, a.argmax_vis = argmax_vis;
+                                 a.range_word = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
+                                 a.pair_j = pair_j, a.tile_info = tiles, a.counters = counters, a.pair_vis = pair_vis;
+                                 hipLaunchKernelGGL(k_dvis_x6t<true>, grid, dim3(256), 0, s, a);
+                               });
 }

@@ -581,6 +581,47 @@ def test_streaming_kernel_equals_one_point_per_workgroup_kernel(dev, vis_net):
         ops.range_check(sync=True)
 
 
+@pytest.mark.parametrize("precision,gen", [("f16x1", 1), ("f16x1", 2), ("f16x1", 3), ("f16x6-stream", None)])
+def test_f16_and_x6_tile_list_forms_for_any_number_of_workgroups(dev, vis_net, precision, gen):
+    """The persistent kernels of the f16 throughput mode (csrc/vis_diffuse_f16t.hip generations 1 and 2, the point-block form of
+    csrc/vis_diffuse_f16p.hip) and the exact-operand tile-list form (k_dvis_x6t<stream>) give the same bits for any number of persistent
+    workgroups: one that walks every round with the weight ring running across rounds, two, a number that does not divide the rounds,
+    and 4096, where most workgroups have no round and leave early.  33 points in two chunks whose boundary lies inside a 16-point block,
+    6 x 8 = 48 directions per point: about two tiles per point survive the cull -- the f16 tile list runs five rounds with a ragged last
+    one, the point-block form about a dozen."""
+    from robir_amd import ops, sg_render, synth
+    g = np.random.Generator(np.random.PCG64(33))
+    n, C, L, nsamp = 33, 2, 6, 8
+    pts = torch.from_numpy((g.standard_normal((n, 3)) * 0.25).astype(np.float32)).to(dev)
+    nrm = torch.from_numpy(g.standard_normal((n, 3)).astype(np.float32)).to(dev)
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True)
+    lgt = torch.from_numpy(synth.synth_light_sgs(3, L)).to(dev)
+    u = torch.from_numpy(g.random((2, C, L, nsamp), dtype=np.float32)).to(dev)
+    cid = torch.from_numpy((np.arange(n) >= 20).astype(np.int32)).to(dev)      # ascending; the boundary inside block 16 .. 31
+    old_p, old_w, old_g = sg_render.VIS_PRECISION, ops.DVIS_STREAM_WORKGROUPS, ops.DVIS_F16_GEN
+    try:
+        sg_render.VIS_PRECISION = precision
+        if gen is not None:
+            ops.DVIS_F16_GEN = gen
+        res = {}
+        for wgs in (0, 1, 2, 3, 4096):
+            ops.DVIS_STREAM_WORKGROUPS = wgs
+            for am in (False, True):
+                st = {}
+                res[wgs, am] = (sg_render._diffuse_vis_core(pts, nrm, vis_net, lgt, u[0], u[1], 1.0, am, cid, C, st), int(st["diffuse_vis_evals"]))
+        for am in (False, True):
+            ref, evals = res[0, am]
+            assert evals > 0 and not torch.isnan(ref).any()
+            for wgs in (1, 2, 3, 4096):
+                v, e = res[wgs, am]
+                assert e == evals, (wgs, am, e, evals)
+                assert not torch.isnan(v).any(), (wgs, am)
+                assert torch.equal(v, ref), (wgs, am, float((v - ref).abs().max()))
+        ops.range_check(sync=True)
+    finally:
+        sg_render.VIS_PRECISION, ops.DVIS_STREAM_WORKGROUPS, ops.DVIS_F16_GEN = old_p, old_w, old_g
+
+
 def test_light_visibility_arithmetic_vs_float64(dev, vis_net, oracle_sd, monkeypatch):
     """The default light-visibility kernel since round 6 forms the two outer products of the 2^-22 class (h.xl, l.xh) from bf8 copies of their
     operands (csrc/vis_diffuse_x6t.hip, XT_FP8).  Anchored on a FLOAT64 evaluation of the reference's formulas (oracle, same points,
