@@ -577,7 +577,4 @@ int rb_exr_piz_decode(const unsigned char* src, long n_src, const int* chan, int
 #ifdef __cplusplus
 }
 #endif
-#ifdef RB_LEGACY        /* the legacy library is a superset: its translation units see both sets of prototypes */
-#include "robir_hip_legacy.h"
-#endif
 #endif /* ROBIR_HIP_H */

@@ -1,8 +1,8 @@
 /* include/robir_hip_legacy.h -- the RETIRED entry points of librobir_hip (round 5).
  *
  * None of these is in the default library `robir_amd/librobir_hip.so` (ABI version 8, include/robir_hip.h) and no default precision
- * policy calls them.  `make -C robir_amd/csrc legacy` builds `robir_amd/librobir_hip_legacy.so`, a SUPERSET of the default library compiled
- * with -DRB_LEGACY, which exports them next to everything robir_hip.h declares; robir_amd/_lib.py loads it on demand
+ * policy calls them.  `make -C robir_amd/csrc legacy` builds `robir_amd/librobir_hip_legacy.so`, a SUPERSET of the default library: the same
+ * objects plus the sources that define these, so it exports them next to everything robir_hip.h declares; robir_amd/_lib.py loads it on demand
  * (`ROBIR_PRECISION=split`, the bit-identity tests that compare kernel generations, `ROBIR_SDF_FUSED_PE=0`).  What lives here:
  *   - the split-precision family of rounds 1-2 ((hi, lo) f16 operand pairs, 22 bits): k_dvis_v2 / k_dvis3_* (rb_dvis_fused_v2,
  *     rb_dvis_stream), k_sdf_ring / k_sdf_ring8 + k_sdf_back (rb_sdf_*ring*, rb_sdf_value_grad*), k_color_ring8, k_wide_ring, and their

@@ -13,7 +13,7 @@
 //   layer    0    1    2    3    4          K   320  256  256  256  256
 //   chunks  16   16   16   16    1      first     0   16   32   48   64          65 chunks = 1 (mod 4): the slot table rotates by one
 //   slices per wave and chunk (1 KB each; wave v copies slices v, v + 8 (, v + 16)): 3 for K = 320 (24 KB requested, 20 KB used), 2 after
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include <type_traits>

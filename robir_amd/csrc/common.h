@@ -32,11 +32,13 @@ inline dim3 grid1d(long n, int per_block) {
 enum { RB_RANGE_DVIS = 0, RB_RANGE_VIS, RB_RANGE_SDF, RB_RANGE_COLOR, RB_RANGE_WIDE, RB_RANGE_SOFTPLUS512, RB_RANGE_WORDS = 8 };
 unsigned* range_flags();
 
-// reverse-mode SDF gradient on the f32-input MFMA: the two kernels live with the first-generation engine (mlp_kernels.hip), the
-// entry point with the other gradient paths (sdf_back.hip)
+// Host-side launchers of the reverse-mode SDF gradient (entry points: sdf_value_grad.hip; the legacy split-precision form: sdf_back.hip).
+// The two passes on the f32-input MFMA, with the other kernels of that engine (mlp_f32.hip):
 int launch_sdf_f32_store(const float* xyz, long M, float in_scale, const float* Wp, float out_scale, float* out0, float* sig,
                          hipStream_t s);
 int launch_sdf_back_f32(const float* sig, long M, const float* Wt, const float* w8row, float* gfeat, hipStream_t s);
+// k_pe_grad_points, the contraction that ends every form (sdf_value_grad.hip).  Launch only: the caller checks it under its own name
+void launch_pe_grad_points(const float* gfeat, const float* xyz, float in_scale, long M, float grad_scale, float* grad, hipStream_t s);
 int launch_sdf_back_x6(const float* sig, long M, const float* Wt, const float* w8row, float* gfeat, hipStream_t s);                       // sdf_back_x6.hip
 int launch_sdf_x6_store(const float* x, long M, float in_scale, const float* Wp, float out_scale, float* out0, float* sig, hipStream_t s);   // sdf_x6.hip
 

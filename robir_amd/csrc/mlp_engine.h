@@ -625,7 +625,7 @@ __device__ __forceinline__ void load_features(const float* __restrict__ X, long 
 
 // Positional encoding fused into the network kernels: rows are not read but ENCODED IN THE KERNEL from the points xyz[M,3] (x in_scale), cooperatively: the lanes that share a point
 // (four for value rows; sixteen when a tile holds the value row and the three tangent rows of four points) evaluate its 30
-// (frequency, axis) sincosf pairs between them -- the calls k_feat_pe10 (mlp_kernels.hip; model/embedder.py:17-38) fills the rows with, so the operands are bit-identical --
+// (frequency, axis) sincosf pairs between them -- the calls k_feat_pe10 (feat.hip; model/embedder.py:17-38) fills the rows with, so the operands are bit-identical --
 // and exchange them through a 4 KB LDS scratch per tile (same wave, in-order LDS: no barrier).  8 resp. 2 sincosf per lane and
 // tile instead of a 256 B (1 KB with tangent rows) row per point and the encoding launch.
 // the 63 encoded columns of one point written by the four lanes (g = 0..3) that share its row: frow[0..62]

@@ -1,9 +1,9 @@
-// Split-precision (f16x3) forms of the stand-alone MLP kernels of mlp_kernels.hip: same networks, same packed-chunk weight
+// Split-precision (f16x3) forms of the stand-alone MLP kernels of mlp_f32.h: same networks, same packed-chunk weight
 // stream (an f16x3 chunk has the byte size of the fp32 chunk of the same K), layers on v_mfma_f32_16x16x32_f16 through
 // dense_layer_h3 (mlp_engine.h): x*w = xh*wh + xh*wl + xl*wh with fp32 accumulation, operands lifted by a power of two
 // before the hi/lo split so that both halves are normal f16 numbers.  A separate translation unit only to keep the
 // build parallel.
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 

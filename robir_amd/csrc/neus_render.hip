@@ -1,7 +1,7 @@
 // NeuS ray-march with hierarchical sampling: the non-MLP parts of render_neus / up_sample / sample_pdf / cat_z_vals /
 // render_core (model/sdf_render.py:37-132,175-374) and of NormalTrainRunner.get_neus_surface
 // (training/train_normal.py:239-286).  The SDF / gradient / colour evaluations between these steps are the MFMA
-// kernels of mlp_kernels.hip; everything here is one thread per ray over <= 128 samples, fp32, reference rounding
+// kernels of mlp_f32.h; everything here is one thread per ray over <= 128 samples, fp32, reference rounding
 // (-ffp-contract=off).
 #include "../../include/robir_hip.h"
 #include "common.h"

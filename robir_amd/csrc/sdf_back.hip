@@ -5,7 +5,7 @@
 //     g7 = W8[0,:],   gz_l = g_l (.) sig_l,   g_{l-1} = W_l^T gz_l        (l = 7 .. 1),      d/d(features) = W_0^T gz_0,
 // with the skip connection of layer 4 (input = [act(layer 3) | features] / sqrt 2) splitting W_4^T gz_4 into the part that
 // continues (193 slots) and a direct contribution to the feature gradient.  The contraction with the Jacobian of the positional
-// encoding is a small element-wise kernel (k_pe_grad below).  2x the matrix work of the values instead of 4x, and the backward
+// encoding is a small element-wise kernel (k_pe_grad below on feature rows, k_pe_grad_points of sdf_value_grad.hip on points).  2x the matrix work of the values instead of 4x, and the backward
 // epilogue is a multiply + split (no transcendentals).
 //
 // Same machine as sdf_ring.hip: one cyclic stream of 120 chunks (16 output slots x K) per round of 128 points through a 4-slot
@@ -27,7 +27,7 @@
 //     (sigmoids are >= 0) and re-reads while it still finds one.
 // The 32 rows of layer-7 sigmoids that open a round are ordinary loads into the operand registers that are idle after B7,
 // issued at the end of a round and waited for in full at the top of the next.
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include <cstdio>
@@ -501,38 +501,14 @@ __global__ void k_pe_grad(const float* __restrict__ gfeat, const float* __restri
   grad[i] = acc * grad_scale;
 }
 
-// The same contraction with the encoding recomputed from the points (the fused form keeps no feature rows): the same sincosf of
-// the same argument as the features the value pass used.
-__global__ void k_pe_grad_points(const float* __restrict__ gfeat, const float* __restrict__ xyz, float in_scale, long M,
-                                 float grad_scale, float* __restrict__ grad) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= 3 * M) return;
-  const long m = i / 3;
-  const int c = (int)(i - 3 * m);
-  const float* gf = gfeat + m * 128;
-  const float a = xyz[i] * in_scale;
-  float acc = gf[c] + gf[64 + c];
-#pragma unroll 1
-  for (int k = 0; k < 10; ++k) {
-    const float f = (float)(1 << k);
-    float sn, cs;
-    sincosf(a * f, &sn, &cs);
-    const int is = 3 + 6 * k + c, ic = is + 3;
-    acc += f * ((gf[is] + gf[64 + is]) * cs - (gf[ic] + gf[64 + ic]) * sn);
-  }
-  grad[i] = acc * grad_scale;
-}
-
 }  // namespace rb
 
 using namespace rb;
 
-#ifdef RB_LEGACY
 extern "C" long rb_sdf_value_grad_scratch_floats(long M) {
   const long rounds = (M + 127) / 128;
   return rounds * (SB_SIG_ROUND_F4 * 4 + 128L * 128);
 }
-#endif  // RB_LEGACY
 
 // X != nullptr: feature rows; X == nullptr: points xyz[M,3] x in_scale with the encoding fused into the value pass
 static int sdf_value_grad_impl(const float* X, const float* xyz, float in_scale, long M, const float* Wp, const float* Wb,
@@ -541,16 +517,8 @@ static int sdf_value_grad_impl(const float* X, const float* xyz, float in_scale,
   if (M <= 0) return 0;
   RB_REQUIRE((X || xyz) && Wp && Wb && w8row && out0 && grad && scratch, "null pointer");
   const long rounds = (M + 127) / 128;
-  if (n_workgroups <= 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return rb::fail(__func__, "device query failed");
-      cus = prop.multiProcessorCount;
-    }
-    n_workgroups = cus;
-  }
+  if (n_workgroups <= 0) n_workgroups = rb::device_cus();
+  if (n_workgroups <= 0) return rb::fail(__func__, "device query failed");
   const unsigned grid = (unsigned)(rounds < n_workgroups ? rounds : n_workgroups);
   const float us = ldexpf(1.0f, -scale_log2);
   hipStream_t s = (hipStream_t)stream;
@@ -586,57 +554,11 @@ static int sdf_value_grad_impl(const float* X, const float* xyz, float in_scale,
   if (X) {
     hipLaunchKernelGGL(k_pe_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gfeat, X, M, grad_scale, grad);
   } else {
-    hipLaunchKernelGGL(k_pe_grad_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gfeat, xyz, in_scale, M, grad_scale, grad);
+    launch_pe_grad_points(gfeat, xyz, in_scale, M, grad_scale, grad, s);
   }
   return check_launch("k_pe_grad");
 }
 
-// The same op at the reference's precision (exact policy): k_sdf_mlp<5> (f32-input MFMA, sigmoid tiles out), k_sdf_back_f32,
-// k_pe_grad_points.  scratch: rb_sdf_value_grad_f32_scratch_floats(M) floats.
-extern "C" long rb_sdf_value_grad_f32_scratch_floats(long M) {
-  const long tiles = (M + 127) / 128 * 8;
-  return tiles * (8L * 16 * 64 * 4) + ((M + 127) / 128 * 128) * 128L;
-}
-extern "C" int rb_sdf_value_grad_f32_points(const float* x, long M, float in_scale, const float* Wp, const float* Wt, const float* w8row,
-                                            float out_scale, float grad_scale, float* out0, float* grad, float* scratch,
-                                            rb_stream_t stream) {
-  if (M <= 0) return 0;
-  RB_REQUIRE(x && Wp && Wt && w8row && out0 && grad && scratch, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const long tiles = (M + 127) / 128 * 8;
-  float* sig = scratch;
-  float* gfeat = scratch + tiles * (8L * 16 * 64 * 4);
-  int rc = launch_sdf_f32_store(x, M, in_scale, Wp, out_scale, out0, sig, s);
-  if (rc) return rc;
-  rc = launch_sdf_back_f32(sig, M, Wt, w8row, gfeat, s);
-  if (rc) return rc;
-  const long n = 3 * M;
-  hipLaunchKernelGGL(k_pe_grad_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gfeat, x, in_scale, M, grad_scale, grad);
-  return check_launch("k_pe_grad_points");
-}
-
-// ... with both passes on exact three-piece operands: same scratch.  two_tile = 0: k_sdf_x6<5> (csrc/sdf_x6.hip, Wp = packing.pack_sdf_x6)
-// + k_sdf_back_x6 (csrc/sdf_back_x6.hip, Wt = packing.pack_sdf_back_x6), one 16-row tile per wave; two_tile = 1: k_sdf_x6t<5> +
-// k_sdf_back_x6t (csrc/sdf_x6t.hip, sdf_back_x6t.hip; Wt = packing.pack_sdf_back_x6(two_tile=True): W3^T's K padded to 256).
-extern "C" int rb_sdf_value_grad_x6_points(const float* x, long M, float in_scale, const float* Wp, const float* Wt, const float* w8row,
-                                           float out_scale, float grad_scale, float* out0, float* grad, float* scratch, int two_tile,
-                                           rb_stream_t stream) {
-  if (M <= 0) return 0;
-  RB_REQUIRE(x && Wp && Wt && w8row && out0 && grad && scratch, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const long tiles = (M + 127) / 128 * 8;
-  float* sig = scratch;
-  float* gfeat = scratch + tiles * (8L * 16 * 64 * 4);
-  int rc = two_tile ? launch_sdf_x6t(x, M, in_scale, Wp, 5, out_scale, out0, sig, 0, s) : launch_sdf_x6_store(x, M, in_scale, Wp, out_scale, out0, sig, s);
-  if (rc) return rc;
-  rc = two_tile ? launch_sdf_back_x6t(sig, M, Wt, w8row, gfeat, s) : launch_sdf_back_x6(sig, M, Wt, w8row, gfeat, s);
-  if (rc) return rc;
-  const long n = 3 * M;
-  hipLaunchKernelGGL(k_pe_grad_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gfeat, x, in_scale, M, grad_scale, grad);
-  return check_launch("k_pe_grad_points");
-}
-
-#ifdef RB_LEGACY
 extern "C" int rb_sdf_value_grad(const float* X, long M, const float* Wp, const float* Wb, const float* w8row, int scale_log2,
                                  float out_scale, float grad_scale, float* out0, float* grad, float* scratch, int n_workgroups,
                                  rb_stream_t stream) {
@@ -652,4 +574,3 @@ extern "C" int rb_sdf_value_grad_points(const float* x, long M, float in_scale, 
   return sdf_value_grad_impl(nullptr, x, in_scale, M, Wp, Wb, w8row, scale_log2, out_scale, grad_scale, out0, grad, scratch,
                              n_workgroups, stream);
 }
-#endif  // RB_LEGACY

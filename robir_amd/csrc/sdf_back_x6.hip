@@ -1,5 +1,5 @@
 // d sdf / d (encoded input) by reverse mode with EXACT fp32 operands on the f16 matrix pipe ("f16x6") -- the default precision
-// policy's gradient pass, round 3: k_sdf_back_f32 (mlp_kernels.hip, f32-input MFMA) on the one-tile machine of x6_ring.h (sx_layer).
+// policy's gradient pass, round 3: k_sdf_back_f32 (mlp_f32.hip, f32-input MFMA) on the one-tile machine of x6_ring.h (sx_layer).
 //
 // In: the sigmoid tiles the value pass stored (k_sdf_x6<5> / k_sdf_mlp<5>: [tile = row / 16][layer 8][chunk 16][lane 64] float4).
 // Out: two 64-wide gradient rows per point (layer 0's and the skip connection's share; k_pe_grad_points contracts them with the
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6(const f4* __restrict__ s
   __syncthreads();
 }
 
-// host-side launcher for sdf_back.hip (rb_sdf_value_grad_x6_points)
+// host-side launcher for sdf_value_grad.hip (rb_sdf_value_grad_x6_points)
 int launch_sdf_back_x6(const float* sig, long M, const float* Wt, const float* w8row, float* gfeat, hipStream_t s) {
   const int pg = persistent_grid((M + 63) / 64, 0);
   if (pg <= 0) return rb::fail(__func__, "device query failed");

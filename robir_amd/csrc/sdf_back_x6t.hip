@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void k_sdf_back_x6t(const f4* __restrict__ 
   __syncthreads();
 }
 
-// host-side launcher for sdf_back.hip (rb_sdf_value_grad_x6_points)
+// host-side launcher for sdf_value_grad.hip (rb_sdf_value_grad_x6_points)
 int launch_sdf_back_x6t(const float* sig, long M, const float* Wt, const float* w8row, float* gfeat, hipStream_t s) {
   const int pg = persistent_grid((M + 127) / 128, 0);
   if (pg <= 0) return rb::fail(__func__, "device query failed");

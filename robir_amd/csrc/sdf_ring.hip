@@ -15,7 +15,7 @@
 //   * the output layer's values are stored from the same slots (no 68-register output array in the full mode).
 // Arithmetic per element is that of the first generation (same scales, same product order): results agree to fp32 rounding
 // of the softplus evaluation order, the tests hold both to the oracle.
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include <cstdlib>
@@ -608,16 +608,8 @@ extern "C" int rb_sdf_mlp_ring(const float* X, long M, const float* Wp, int mode
   RB_REQUIRE(mode < 2 || grad, "gradient output missing");
   const long MR = mode >= 2 ? 4 * M : M;
   const long rounds = (MR + 127) / 128;
-  if (n_workgroups <= 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return rb::fail(__func__, "device query failed");
-      cus = prop.multiProcessorCount;
-    }
-    n_workgroups = cus;
-  }
+  if (n_workgroups <= 0) n_workgroups = rb::device_cus();
+  if (n_workgroups <= 0) return rb::fail(__func__, "device query failed");
   const unsigned grid = (unsigned)(rounds < n_workgroups ? rounds : n_workgroups);
   const float us = ldexpf(1.0f, -scale_log2);
   unsigned* rw = range_flags() ? range_flags() + RB_RANGE_SDF : nullptr;
@@ -641,16 +633,8 @@ extern "C" int rb_sdf_points_ring_jvp(const float* x, long M, float in_scale, co
   RB_REQUIRE(x && Wp && out0 && grad, "null pointer");
   RB_REQUIRE(mode == 2 || mode == 3, "mode: 2 = distance + gradient, 3 = all 257 outputs + gradient");
   const long MR = 4 * M, rounds = (MR + 127) / 128;
-  if (n_workgroups <= 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return rb::fail(__func__, "device query failed");
-      cus = prop.multiProcessorCount;
-    }
-    n_workgroups = cus;
-  }
+  if (n_workgroups <= 0) n_workgroups = rb::device_cus();
+  if (n_workgroups <= 0) return rb::fail(__func__, "device query failed");
   const unsigned grid = (unsigned)(rounds < n_workgroups ? rounds : n_workgroups);
   const float us = ldexpf(1.0f, -scale_log2);
   unsigned* rw = range_flags() ? range_flags() + RB_RANGE_SDF : nullptr;
@@ -673,16 +657,8 @@ extern "C" int rb_sdf_points_ring(const float* x, long M, float in_scale, const 
   RB_REQUIRE(x && Wp && out0, "null pointer");
   RB_REQUIRE(mode == 0 || mode == 1, "mode: 0 = signed distance, 1 = all 257 outputs (gradients: rb_sdf_value_grad_points)");
   const long rounds = (M + 127) / 128;
-  if (n_workgroups <= 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return rb::fail(__func__, "device query failed");
-      cus = prop.multiProcessorCount;
-    }
-    n_workgroups = cus;
-  }
+  if (n_workgroups <= 0) n_workgroups = rb::device_cus();
+  if (n_workgroups <= 0) return rb::fail(__func__, "device query failed");
   const unsigned grid = (unsigned)(rounds < n_workgroups ? rounds : n_workgroups);
   return rb::launch_sdf_ring8(mode, nullptr, x, in_scale, M, (const f4*)Wp, ldexpf(1.0f, -scale_log2), out_scale, out0, nullptr, grid,
                               (hipStream_t)stream);

@@ -14,7 +14,7 @@
 // -- 1 / 2 / 3 slices per wave for K = 64 / 256 / 288, i.e. 8 / 16 / 24 KB per chunk: more than the chunk where K is not 256
 // (the surplus is the following chunk's bytes, never used), so that every wave requests the same number of rows and the
 // counted wait is the same immediate for all of them.
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include <cstdlib>
@@ -57,7 +57,7 @@ __device__ __forceinline__ void s8_wait() {
 // FUSED: the positional encoding is computed HERE from the points xyz[M,3] (x in_scale) instead of being read as rows X[M,64]
 // (model/embedder.py:17-38 + model/neus_model.py:385-417 in one kernel): once per round the four lanes that share a point
 // evaluate its 30 (frequency, axis) sine / cosine pairs between them -- the same sincosf of the same argument as k_feat_pe10
-// (mlp_kernels.hip), so the features and everything downstream are bit-identical to the row form --, exchange them through a
+// (feat.hip), so the features and everything downstream are bit-identical to the row form --, exchange them through a
 // 4 KB LDS scratch per wave and pick up their sixteen B-operand features.  8 x 16 x 30 sincosf per round of 142 chunks: 1 % of
 // the round; the 256 B per point of feature rows and the encoding kernel disappear.
 template <int MODE, bool FUSED>

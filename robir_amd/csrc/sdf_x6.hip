@@ -1,7 +1,7 @@
 // NeuS SDF network (model/neus_model.py:385-438) with EXACT fp32 operands on the f16 matrix pipe ("f16x6") -- the value pass of the
 // default precision policy, round 3.
 //
-// Under the exact policy the SDF net ran on v_mfma_f32_16x16x4_f32 (k_sdf_mlp, mlp_kernels.hip): 0.69 of a 157 TFLOP/s peak, 49 % of
+// Under the exact policy the SDF net ran on v_mfma_f32_16x16x4_f32 (k_sdf_mlp, mlp_f32.h): 0.69 of a 157 TFLOP/s peak, 49 % of
 // BASELINE config 2 at the reference's precision.  This kernel carries every operand as three halves and keeps the six partial products
 // of weight >= 2^-22 in three fp32 accumulators by weight class -- the arithmetic of k_dvis_x6 (vis_diffuse_x6.hip: exact operands,
 // not narrower than an fp32 fma chain; bound 2500 / 6 = 417 TFLOP/s) -- on the chunk-stream machine of wide_ring.h: persistent
@@ -10,7 +10,7 @@
 // chunk in its middle, fragment reads running across the chunk boundary, the softplus + three-way split of chunk j between the MFMAs
 // of chunk j+1, the positional encoding computed in the kernel.  The unit loop is sx_layer (x6_ring.h), the stream geometry x6_layout.h.
 // MODE 0: signed distance only -> out0[M].   MODE 1: all 257 outputs -> out0[M,257].   MODE 5: MODE 1 + sigmoid(100 z) of every hidden
-// pre-activation -> sig [tile = row / 16][layer 8][chunk 16][lane 64] float4, the layout k_sdf_back_f32 (mlp_kernels.hip) reads.
+// pre-activation -> sig [tile = row / 16][layer 8][chunk 16][lane 64] float4, the layout k_sdf_back_f32 (mlp_f32.hip) reads.
 // Weights: packing.pack_sdf_x6 (rb_pack_layer_x6, scale 2^0; K padded to 64, 256 x3, 288 = [208 | 64 | 16 zero], 256 x4).
 #include "../../include/robir_hip.h"
 #include "common.h"
@@ -290,7 +290,7 @@ int rb_sdf_x6_points(const float* x, long M, float in_scale, const float* Wp, in
 
 }  // extern "C"
 
-// value + reverse-mode gradient with the value pass on exact operands: k_sdf_x6<5>, k_sdf_back_f32, k_pe_grad_points (sdf_back.hip)
+// value + reverse-mode gradient with the value pass on exact operands: k_sdf_x6<5>, k_sdf_back_f32, k_pe_grad_points (sdf_value_grad.hip)
 namespace rb {
 int launch_sdf_x6_store(const float* x, long M, float in_scale, const float* Wp, float out_scale, float* out0, float* sig, hipStream_t s) {
   return sx_launch(x, M, in_scale, Wp, 5, out_scale, out0, sig, 0, s);

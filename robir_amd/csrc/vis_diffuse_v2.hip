@@ -13,6 +13,7 @@
 //   * the relu + hi/lo split of a chunk's result runs under the next chunk's MFMAs and writes straight into the next
 //     layer's operand registers (no fp32 copy of the layer output);
 //   * the 256->2 head is a 49th, LDS-resident chunk on the matrix pipe.
+#include "../../include/robir_hip_legacy.h"
 #include "dvis_tiles.h"
 #include "mlp_engine.h"
 #include <cstdlib>

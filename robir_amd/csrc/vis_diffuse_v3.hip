@@ -20,6 +20,7 @@
 // synchronises.
 // k_dvis3_cull / k_dvis3_reduce, the tile record and the host side of a launch are shared with the exact-operand and f16 forms of the
 // default library: dvis_tiles.h / dvis_tiles.hip (round 5: this file is legacy-only).
+#include "../../include/robir_hip_legacy.h"
 #include "dvis_tiles.h"
 #include "mlp_engine.h"
 #include <cstdlib>

@@ -21,6 +21,7 @@
 // between the MFMAs of the current one, the 256 -> 2 head as a 49th LDS-resident chunk.  A chunk's 48 MFMAs are issued as
 // six runs of eight on one accumulator each (wl.xh, wm.xm, wh.xl | wm.xh, wh.xm | wh.xh): a weight piece's registers are
 // refilled with the next chunk's as soon as its last run has issued.
+#include "../../include/robir_hip_legacy.h"
 #include "dvis_tiles.h"
 #include "mlp_engine.h"
 

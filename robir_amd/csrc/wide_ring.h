@@ -12,7 +12,7 @@
 // a 4-slot bias ring): a bias table of the whole net (16 KB) would not fit beside 4 x 34 KB of ring and the encoder's scratch.
 // Same products in the same order, same lifts, same epilogue arithmetic as the first generation: bit-identical outputs.
 #pragma once
-#include "../../include/robir_hip.h"
+#include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
 #include <type_traits>

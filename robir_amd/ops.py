@@ -280,7 +280,7 @@ def sdf_points_jvp_h3(x, M, blob, full, scale_log2, in_scale=1.0, out_scale=1.0,
     return out0, grad
 
 
-SDF_GRAD = os.environ.get("ROBIR_SDF_GRAD", "reverse")     # "reverse" (csrc/sdf_back.hip) | "forward" (mode 3 rows)
+SDF_GRAD = os.environ.get("ROBIR_SDF_GRAD", "reverse")     # "reverse" (csrc/sdf_value_grad.hip; split precision: sdf_back.hip) | "forward" (mode 3 rows)
 SDF_GRAD_MIN_POINTS = 16384       # below this the three-launch reverse form does not pay (0.25 ms floor; measured crossover)
 SDF_GRAD_F32_MIN_POINTS = 16384   # ... of the f32-input-MFMA form (three launches against one of the four-row forward-mode kernel)
 SDF_GRAD_SLAB = 1 << 20           # points per slab of the reverse form (8.5 KB of scratch per point)
@@ -333,7 +333,7 @@ def sdf_value_grad(x, M, blob, back, scale_log2, in_scale=1.0, out_scale=1.0):
 
 
 def sdf_value_grad_f32(x, M, blob, back, in_scale=1.0, out_scale=1.0):
-    """sdf_value_grad at the reference's precision (f32-input MFMA; csrc/mlp_kernels.hip k_sdf_mlp<5> + k_sdf_back_f32): x [M,3] ->
+    """sdf_value_grad at the reference's precision (f32-input MFMA; csrc/mlp_f32.h, mlp_f32.hip k_sdf_mlp<5> + k_sdf_back_f32): x [M,3] ->
     out [M,257], grad [M,3].  blob = packing.pack_sdf(full=True), back = packing.pack_sdf_back."""
     wt, w8 = back
 

@@ -268,7 +268,7 @@ def pack_sdf_back_h3(sd, device):
 
 
 def pack_sdf_back(sd, device):
-    """pack_sdf_back_h3 for the f32-input MFMA (rb_sdf_value_grad_f32_points, k_sdf_back_f32 in csrc/mlp_kernels.hip): W7^T, W6^T, W5^T,
+    """pack_sdf_back_h3 for the f32-input MFMA (rb_sdf_value_grad_f32_points, k_sdf_back_f32 in csrc/mlp_f32.hip): W7^T, W6^T, W5^T,
     W4^T as [193 continuing rows -> 208 | 63 skip-feature rows -> 64] (N = 272), W3^T (K 193 -> 208), W2^T, W1^T, W0^T (N 63 -> 64),
     no biases; and row 0 of layer 8.  -> (blob, w8row [256])."""
     sdt = {k: _t(sd, k) for k in sd if k.startswith(SDF)}

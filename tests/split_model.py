@@ -2,7 +2,7 @@
 instruction, so that tests can hold the device to it bit for bit (tests/test_split_cpu.py: the model's own properties, no GPU;
 tests/test_mlp_gpu.py: rb_pack_layer_x6 and pack_vis_split's bf8 blob against it; tests/test_precision_gpu.py: the windows below).
 
-  split_weight      csrc/mlp_kernels.hip k_pack_layer_x6: w 2^s = h + m 2^-11 + l 2^-22, three round-to-nearest casts, residuals in fp32
+  split_weight      csrc/pack.hip k_pack_layer_x6: w 2^s = h + m 2^-11 + l 2^-22, three round-to-nearest casts, residuals in fp32
   split_activation  csrc/x6_ring.h sx_split_pair: h, m by v_cvt_pkrtz (round toward zero, finite values clamp at 65504), l by
                     v_fma_mixlo_f16 (round to nearest even); f16 subnormals carried, nothing flushed
   bf8_trunc         the activations' bf8 (e5m2) copies in csrc/vis_diffuse_x6t.hip: the top byte of the f16 pattern (v_perm_b32)

@@ -53,6 +53,37 @@ def test_error_reporting_without_gpu():
                                ctypes.c_void_p(0)) == 0
 
 
+def test_default_library_refuses_dvis_precision_5():
+    """rb_dvis_fused's precision 5 is linked into the legacy library only (csrc/vis_diffuse_h3.hip); the default library links a refusal
+    in its place (csrc/vis_diffuse_h3_stub.hip): return code 1 and this text, after the argument checks, nothing dereferenced or launched."""
+    import ctypes
+    from robir_amd import _lib
+    L = _lib.lib()
+    buf = (ctypes.c_float * 16)()
+    p = ctypes.c_void_p(ctypes.addressof(buf))
+    rc = L.rb_dvis_fused(p, ctypes.c_void_p(0), ctypes.c_long(1), p, p, p, p, p, p, p, p, ctypes.c_int(2), ctypes.c_int(8), ctypes.c_int(0),
+                         ctypes.c_int(5), ctypes.c_int(0), p, ctypes.c_void_p(0), ctypes.c_void_p(0))
+    assert rc == 1
+    assert L.rb_last_error() == (b"rb_dvis_fused: precision 5 (first-generation split-precision kernel) is built into "
+                                 b"librobir_hip_legacy.so only (make legacy)")
+
+
+def test_each_library_keeps_its_own_error_state():
+    """The legacy library links its own copy of csrc/runtime.hip: a failing call there sets its rb_last_error() and leaves the default
+    library's string alone.  (Checked where the legacy library has been built.)"""
+    import ctypes
+    from robir_amd import _lib
+    L, null = _lib.lib(), ctypes.c_void_p(0)
+    assert L.rb_vis_mlp_points(null, null, ctypes.c_long(8), ctypes.c_int(1), null, null, null) != 0
+    before = L.rb_last_error()
+    assert before == b"rb_vis_mlp_points: null pointer"
+    if os.path.exists(_lib.LEGACY_PATH):
+        G = _lib.legacy()
+        assert G.rb_vis_mlp(null, ctypes.c_long(8), null, null, null) != 0
+        assert G.rb_last_error() == b"rb_vis_mlp: null pointer"
+        assert L.rb_last_error() == before
+
+
 def test_no_oracle_import_in_product():
     """The product package must never import the oracle (test infrastructure)."""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "robir_amd")):

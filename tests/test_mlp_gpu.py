@@ -934,3 +934,62 @@ def test_vis_split_fp8_blob_bit_for_bit(dev):
     assert np.array_equal(got6.view(np.uint32), model.view(np.uint32))
     got8 = split["hidden_x6_head_fp8"].cpu().numpy()
     assert np.array_equal(got8.view(np.uint32), sm.repack_fp8(model, ((256, 49),)).view(np.uint32))
+
+
+def test_default_and_legacy_library_agree_in_one_process(dev, synth_weights):
+    """The legacy library links the common objects of the default one plus its own sources (csrc/Makefile).  Both loaded in one process,
+    at the smallest shapes that cross a workgroup boundary: an entry point both export gives the same bits from either (the cross-file
+    launchers of the reverse-mode SDF gradient; the fp32 light-visibility kernel), the feature-row forms of the legacy library the bits
+    of the point form of the default one, and rb_dvis_fused's precision 5 runs where it is linked."""
+    import ctypes
+    from robir_amd import _lib, ops, packing
+    from robir_amd._lib import ptr, stream_ptr
+    c_long, c_int, c_float = ctypes.c_long, ctypes.c_int, ctypes.c_float
+    _lib.legacy()                                                      # absent: the test skips (conftest.py)
+    g = torch.Generator().manual_seed(123)
+    M = 129                                                            # one full 128-row round and a one-row ragged one
+    # rb_sdf_value_grad_f32_points: entry point in sdf_value_grad.hip, the two passes behind launchers in mlp_f32.hip
+    sd = _trained_like(synth_weights, 5)
+    blob, (wt, w8) = packing.pack_sdf(sd, dev, full=True), packing.pack_sdf_back(sd, dev)
+    x = ((torch.rand(M, 3, generator=g) - 0.5) * 1.2).to(dev)
+    n_scratch = _lib.lib().rb_sdf_value_grad_f32_scratch_floats(c_long(M))
+    assert n_scratch == _lib.legacy().rb_sdf_value_grad_f32_scratch_floats(c_long(M))
+
+    def value_grad(call):
+        out, grad = torch.full((M, 257), float("nan"), device=dev), torch.full((M, 3), float("nan"), device=dev)
+        scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
+        call("rb_sdf_value_grad_f32_points", ptr(x), c_long(M), c_float(2.0), ptr(blob), ptr(wt), ptr(w8), c_float(0.5), c_float(1.0),
+             ptr(out), ptr(grad), ptr(scratch), stream_ptr())
+        torch.cuda.synchronize()
+        return out, grad
+    out_d, grad_d = value_grad(_lib.call)
+    out_l, grad_l = value_grad(_lib.call_legacy)
+    assert bool(torch.isfinite(out_d).all()) and bool(torch.isfinite(grad_d).all()) and float(grad_d.abs().max()) > 0.0
+    assert torch.equal(out_d, out_l) and torch.equal(grad_d, grad_l)
+    # rb_vis_mlp_points (default) against rb_feat_vis + rb_vis_mlp (legacy_rows.hip)
+    d = torch.nn.functional.normalize(torch.randn(M, 3, generator=g), dim=-1).to(dev)
+    vb = packing.pack_vis(synth_weights, dev)
+    assert _lib.resolve("rb_vis_mlp_points")[0] is _lib.lib() and _lib.resolve("rb_vis_mlp")[0] is _lib.legacy()
+    assert torch.equal(ops.vis_mlp_points(x, d, vb, rep=1), ops.vis_mlp(ops.feat_vis(x, d, rep=1), vb))
+    # rb_dvis_fused: n = 3 points, L = 2 lobes x 8 samples = one 16-sample tile
+    n, L, nsamp = 3, 2, 8
+    split = packing.pack_vis_split(synth_weights, dev)
+    dirs = torch.nn.functional.normalize(torch.randn(L * nsamp, 3, generator=g), dim=-1).to(dev)
+    nrm = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).to(dev)
+    A, Bd = ops.linear_pe10_256(x[:n].contiguous(), split["point"]), ops.linear_pe10_256(dirs, split["dir"])
+    wdir = (torch.rand(L * nsamp, generator=g) + 0.25).to(dev)
+    wsum = wdir.reshape(L, nsamp).sum(-1).contiguous()
+
+    def dvis(call, precision):
+        out = torch.full((n, L), float("nan"), device=dev)
+        call("rb_dvis_fused", ptr(nrm), ptr(None), c_long(n), ptr(A), ptr(Bd), ptr(dirs), ptr(wdir), ptr(wsum),
+             ptr(split["hidden_h3" if precision == 5 else "hidden"]), ptr(split["w_last"]), ptr(split["b_last"]), c_int(L), c_int(nsamp),
+             c_int(0), c_int(precision), c_int(split["h3_scale_log2"]), ptr(out), ptr(None), stream_ptr())
+        torch.cuda.synchronize()
+        return out
+    v_d, v_l = dvis(_lib.call, 0), dvis(_lib.call_legacy, 0)
+    assert bool(torch.isfinite(v_d).all()) and float(v_d.max()) > 0.0
+    assert torch.equal(v_d, v_l)
+    v5 = dvis(_lib.call_legacy, 5)
+    assert bool(torch.isfinite(v5).all()) and float(v5.min()) >= 0.0 and float(v5.max()) <= 1.0
+    ops.range_check(sync=True)
