@@ -196,9 +196,8 @@ int rb_dvis_fused(const float* normals, const int* chunk_id, long n, const float
  * the 256->2 output layer (rows padded to 16) packed by rb_pack_layer_x6 back to back = 49 chunks, then re-arranged per half chunk
  * of 128 K as [k-block 0..3][h | m][lane][8 halves] (8 KB), [h8: 2 planes][lane][16 bytes] (2 KB), [l8] (2 KB) with byte 4 j + r of
  * a lane's 32 = the e5m2 rounding of half 4 (j % 2) + r of k-block 4 G + j / 2 (robir_amd/packing.py: repack_x6_chunks_fp8): the same
- * size; scale_log2 = 8 NAMES this layout (a library built with -DXT_FP8=0 takes rb_pack_layer_x6's own layout and scale_log2 = 0; a
- * mismatch is refused).  One workgroup of
- * four waves per point, TWO 16-sample tiles per wave (a weight fragment read from the LDS feeds both tiles, a pass of the weights
+ * size; scale_log2 = 8 NAMES this layout and is the only value the entry points take (rb_pack_layer_x6's own layout, scale_log2 = 0,
+ * is refused before any launch).  One workgroup of four waves per point, TWO 16-sample tiles per wave (a weight fragment read from the LDS feeds both tiles, a pass of the weights
  * serves 128 samples), output layer on the matrix pipe.  Other arguments as rb_dvis_fused; vis_out agrees with its precision 0 to
  * fp32 summation order.  The grid is PERSISTENT: min(n, workgroups) workgroups take point after point, in ascending order, from a queue
  * (a library-internal device counter, zeroed on `stream` in front of the launch) and keep the weight ring running across points.

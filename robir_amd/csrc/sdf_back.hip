@@ -43,13 +43,9 @@ constexpr int SB_SLOT_F4 = 1024;          // 16 KB per ring slot (K <= 256: four
 constexpr int SB_NS = 4;                  // ring slots; a chunk is requested SB_NS - 1 iterations before its MFMAs
 constexpr int SB_SS = 8;                  // sigmoid staging sets; a chunk's rows are requested SB_SD iterations before its MFMAs
 constexpr int SB_SD = 6;
-#ifndef SB_WWAIT
-#define SB_WWAIT (8 * (SB_D - 2))
-#endif
-#ifndef SB_FILL
-#define SB_FILL 6
-#endif
 constexpr int SB_D = SB_NS - 1;
+constexpr int SB_WWAIT = 8 * (SB_D - 2);
+constexpr int SB_FILL = 6;
 constexpr int SB_NCHUNK = 120;
 constexpr long SB_SIG_ROUND_F4 = 125L * 2 * 256;     // float4s of the sigmoid blob per round (sdf_ring.hip)
 constexpr float SB_GS = 64.0f;            // operand lift of the gradient rows (power of two)

@@ -23,9 +23,7 @@
 
 namespace rb {
 
-#ifndef SR_FILL
-#define SR_FILL 8
-#endif
+constexpr int SR_FILL = 8;
 constexpr int SR_SLOT_F4 = 1280;          // 20 KB per ring slot: five 4 KB DMA rows (K = 288 needs 4.5)
 
 // The chunk stream of one pass, in closed form (no loops: these fold to constants once the chunk loops are unrolled).

@@ -13,7 +13,8 @@
 // Ring: four slots of 24 KB.  A chunk of K inputs is K/16 KB + bias; wave v copies the 1 KB slices v, v + 8 (, v + 16) of it
 // -- 1 / 2 / 3 slices per wave for K = 64 / 256 / 288, i.e. 8 / 16 / 24 KB per chunk: more than the chunk where K is not 256
 // (the surplus is the following chunk's bytes, never used), so that every wave requests the same number of rows and the
-// counted wait is the same immediate for all of them.
+// counted wait is the same immediate for all of them.  (Staging the copies through registers instead of LDS-DMA measured 10 %
+// slower; a build switch, S8_REGSTAGE, kept that form until commit e16c845.)
 #include "../../include/robir_hip_legacy.h"
 #include "common.h"
 #include "mlp_engine.h"
@@ -218,12 +219,8 @@ __global__ __launch_bounds__(512, 1) void k_sdf_ring8(const float* __restrict__ 
         const int n1 = jb + 1 < NCH ? NP : (jb + 1 == NCH ? NF0 : NF1);
         const int n2 = jb + 2 < NCH ? NP : (jb + 2 == NCH ? NF0 : (jb + 2 == NCH + 1 ? NF1 : NF2));
         const int allowed = n1 + n2;
-#ifndef S8_REGSTAGE
         if (allowed <= 2) s8_wait<2>(); else if (allowed == 3) s8_wait<3>(); else if (allowed == 4) s8_wait<4>();
         else if (allowed == 5) s8_wait<5>(); else s8_wait<6>();
-#else
-        (void)allowed;
-#endif
       }
 #ifndef S8_ABL_NOBAR
       __builtin_amdgcn_s_barrier();
@@ -233,15 +230,6 @@ __global__ __launch_bounds__(512, 1) void k_sdf_ring8(const float* __restrict__ 
       const int n3 = jb + 3 < NCH ? NP : (jb + 3 == NCH ? NF0 : (jb + 3 == NCH + 1 ? NF1 : NF2));
       const f4* src3 = src_of(jb + 3) + 4 + wave * 64;                       // this wave's first 1 KB slice of chunk jb+3
       const unsigned dst3 = ring_b + sl[(jb + 3) & 3] + (unsigned)wave * 1024u;
-#ifdef S8_REGSTAGE
-      // register staging instead of LDS-DMA: this wave's slices of chunk jb+3 are loaded at the top of chunk jb and stored into
-      // the ring slot of chunk jb-1 (free since this chunk's barrier) at its end; in-order LDS puts the stores ahead of the
-      // fragment reads of the next two chunks, whose waits therefore cover them before the barrier of chunk jb+3
-      f4 stg[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-        if (d < n3) stg[d] = src3[d * 512 + lane];
-#endif
       // weight fragments: three k-blocks in registers, read two k-blocks (six MFMAs, ~100 cycles: the LDS latency) ahead
       u4 wfa[3], wfb[3];
       wfa[0] = frag[0];
@@ -290,18 +278,9 @@ __global__ __launch_bounds__(512, 1) void k_sdf_ring8(const float* __restrict__ 
         if (jb > 0 && kb == 0) { yh[(jb - 1) >> 1][0] ^= __builtin_bit_cast(unsigned, accs[(jb - 1) & 1][0]); }
 #endif
 #ifndef S8_ABL_NODMA
-#ifdef S8_REGSTAGE
-        if (kb == KB - 1) {
-          f4* wdst = reinterpret_cast<f4*>(reinterpret_cast<char*>(ring) + sl[(jb + 3) & 3]) + wave * 64 + lane;
-#pragma unroll
-          for (int d = 0; d < 3; ++d)
-            if (d < n3) wdst[d * 512] = stg[d];
-        }
-#else
 #pragma unroll
         for (int d = 0; d < 3; ++d)
           if (d < n3 && (2 * d + 1 < KB ? 2 * d + 1 : KB - 1) == kb) s8_dma16(src3 + d * 512, lane16, dst3 + (unsigned)d * 8192u);
-#endif
 #endif
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -346,18 +325,10 @@ __global__ __launch_bounds__(512, 1) void k_sdf_ring8(const float* __restrict__ 
 #pragma unroll
     for (int d = 0; d < 2; ++d)
       if (d < n) {
-#ifdef S8_REGSTAGE
-        reinterpret_cast<f4*>(reinterpret_cast<char*>(ring) + slot_b[c])[wave * 64 + d * 512 + lane] = (Wp + s8_coff(c) + 4 + wave * 64 + d * 512)[lane];
-#else
         s8_dma16(Wp + s8_coff(c) + 4 + wave * 64 + d * 512, lane16, ring_b + slot_b[c] + (unsigned)wave * 1024u + (unsigned)d * 8192u);
-#endif
       }
   }
-#ifdef S8_REGSTAGE
-  __syncthreads();
-#else
   s8_wait<0>();
-#endif
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 

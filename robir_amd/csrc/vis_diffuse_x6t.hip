@@ -6,13 +6,23 @@
 // 24 KB of LDS-DMA writes next to 192 MFMAs, a quarter of the kernel's time (profiles/r03_*).  Here a wave holds the operands of TWO
 // tiles (2 x 2 x 96 registers: current and next layer), so a fragment feeds two MFMAs and a pass of the weights serves 128 samples:
 // half the LDS traffic per MFMA.  What pays for the registers: the fragments of a chunk are no longer resident (96 registers) but a
-// rolling window of HALF a chunk (4 k-blocks x 3 pieces = 48 registers: a piece's registers are refilled with the next half's right
-// behind the last MFMA that reads them), and next round's table rows are not held across a round (64 registers per tile) but fetched
-// during the head into the registers the next-layer operands have just left.
+// rolling window of HALF a chunk (4 k-blocks x the f16 h and m pieces + the half's two bf8 fragments = 48 registers: a piece's
+// registers are refilled with the next half's right behind the last MFMA that reads them), and next round's table rows are not held
+// across a round (64 registers per tile) but fetched during the head into the registers the next-layer operands have just left.
 //
 // Arithmetic: that of k_dvis_x6 (three-piece operands, six products, one fp32 accumulator per weight class; see its header).  The
 // products of a class are summed half-chunk by half-chunk (h.h | h.m, m.h | h.l, m.m, l.h per four k-blocks), not product by product
 // over the whole chunk: another -- equally valid -- fp32 summation order, so the results differ from k_dvis_x6's in the last bits.
+//
+// Four exact products and two on the bf8 pipe (profiles/r06_fp8_c2.md): of the six products of a multiply-add
+// the two outer ones of the 2^-22 class -- h.xl and l.xh, each with an operand of at most three significant bits -- are formed from bf8
+// (e5m2) copies of their operands on v_mfma_f32_16x16x128_f8f6f4, which does a half chunk's 128 K in one instruction at twice the f16
+// rate: four f16 + two bf8 products = five f16-equivalents instead of six.  The other four products (h.xh | h.xm, m.xh | m.xm) stay
+// exact.  Error against a float64 evaluation: that of six f16 products (the two terms enter at 2^-22 and are right to two or three
+// bits: <= 2^-24 of a product, below what fp32's own accumulation rounds away; tests/test_precision_gpu.py).  Registers and stream: no
+// f16 l pieces of weights or activations; bf8 copies of the h and l pieces stand in their place (weights: packing.repack_x6_chunks_fp8,
+// named by scale_log2 = 8; activations: the top bytes of the f16 pieces, one v_perm_b32 per four values).  (All six products were f16
+// until round 5, and a build switch, XT_FP8, kept that form beside this one; last commit with the switch: e16c845.)
 //
 // The point loop (per-point form; DESIGN section 5.6 item 12, profiles/dvis_persistent_ab.md).  The grid is min(n, one workgroup per CU).
 // A workgroup loads bias_tab and the head chunk and primes the weight ring once, then repeats: take the next point from the queue
@@ -31,34 +41,12 @@
 
 namespace rb {
 
-constexpr int XT_WF4 = 1536;             // weight part of a packed chunk: [kb 8][piece 3][lane 64] x 16 B = 24 KB
+constexpr int XT_WF4 = 1536;             // weight part of a packed chunk: two half chunks of 768 lane-strided 16 B (XT_F16OFF below) = 24 KB
 constexpr int XT_CF4 = 4 + XT_WF4;       // packed chunk in global memory: 16 bias floats + weights
 constexpr int XT_SLOTS = 4, XT_DIST = 3;
 constexpr int XT_PIECES = 6;             // 4 KB rows (1 KB per wave) of one chunk copy
-// Round 6 (XT_FP8, default on; DESIGN section 5.6 item 10, profiles/r06_fp8_c2.md): of the six products of a multiply-add the two outer ones of
-// the 2^-22 class -- h.xl and l.xh, each with an operand of at most three significant bits -- are formed from bf8 (e5m2) copies of their
-// operands on v_mfma_f32_16x16x128_f8f6f4, which does a half chunk's 128 K in one instruction at twice the f16 rate: four f16 + two bf8
-// products = five f16-equivalents instead of six.  The other four products (h.xh | h.xm, m.xh | m.xm) stay exact.  Error against a float64
-// evaluation: unchanged (the two terms enter at 2^-22 and are right to two or three bits: <= 2^-24 of a product, below what fp32's own
-// accumulation rounds away; tests/test_precision_gpu.py).  Register- and stream-neutral: the f16 l pieces of weights and activations are
-// used nowhere else and go; bf8 copies of the h and l pieces take their place (weights: packing.repack_x6_chunks_fp8, named by
-// scale_log2 = 8; activations: the top bytes of the f16 pieces, one v_perm_b32 per four values).  -DXT_FP8=0: six f16 products (rounds 4-5).
-#ifndef XT_FP8
-#define XT_FP8 1
-#endif
-template <int N>
-struct XtInt {
-  static constexpr int value = N;
-};
 // the stage instances of a chunk's epilogue (ep_slot below) that belong to tile 0
 __host__ __device__ constexpr bool xt_slot_tile0(int s) { return s == 0 || s == 1 || (s >= 4 && s <= 7); }
-
-__device__ __forceinline__ void xt_dma16(const f4* gbase_uniform, unsigned lane_byte_off, unsigned lds_byte_uniform) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_byte_uniform), "v"(lane_byte_off),
-               "s"(gbase_uniform)
-               : "memory");
-}
-// (with an immediate offset, and with M0 kept from the copy before: xt_dma16_imm / xt_dma16_keep of x6t_engine.h)
 
 struct XtArgs {
   // both forms
@@ -144,16 +132,15 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
   unsigned voff_a = (unsigned)wave * 6144u + (unsigned)lane * 16u, voff_b = voff_a + 4096u;
   asm volatile("" : "+v"(voff_a), "+v"(voff_b));
   const unsigned wave_lds = ring_b + (unsigned)wave * 6144u;      // + slot * 24576 (+ 4096 for pieces 4, 5) + the immediate
-  // fragment (kb, piece) of a slot: ring_u[slot * XT_WF4 + (kb * 3 + piece) * 64].  Two base registers (slots 0, 1 | 2, 3) keep every
+  // f16 fragment (kb, piece) of a slot: ring_u[slot * XT_WF4 + XT_F16OFF(kb, piece)] (below).  Two base registers (slots 0, 1 | 2, 3) keep every
   // read's offset inside the 16-bit immediate of ds_read_b128 (the ring is 96 KB: from one base the compiler keeps an address
   // register per fragment, parked in the accumulator file and fetched back before every read)
   unsigned ring_a0 = ring_b + (unsigned)lane * 16u, ring_a2 = ring_a0 + 2u * XT_WF4 * 16u;
   asm volatile("" : "+v"(ring_a0), "+v"(ring_a2));
   const xt_lds_u4p ring_u = (xt_lds_u4p)ring_a0, ring_u2 = (xt_lds_u4p)ring_a2;
-  u4 wh[4], wm[4], wl[4];              // rolling window: the fragments of four k-blocks (half a chunk)
-#if XT_FP8
+  u4 wh[4], wm[4];                     // rolling window: the f16 fragments of four k-blocks (half a chunk)
   typedef int xt_i8 __attribute__((ext_vector_type(8)));
-  xt_i8 w8h, w8l;                      // ... and the half's bf8 fragments of the h and l pieces (wl unused)
+  xt_i8 w8h, w8l;                      // ... and the half's bf8 fragments of the h and l pieces
   // a half chunk = 12 KB = 768 lane-strided u4: [k-block 0..3][h | m] (512), h8 (two planes: 128), l8 (128)
 #define XT_F16OFF(KB, PIECE) (((KB) >> 2) * 768 + (((KB) & 3) * 2 + (PIECE)) * 64)
 #define XT_LOAD8(DST, BASE, OFF)                                                                                             \
@@ -161,47 +148,32 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     const u4 a_ = (BASE)[(OFF)], b_ = (BASE)[(OFF) + 64];                                                                    \
     DST = xt_i8{(int)a_[0], (int)a_[1], (int)a_[2], (int)a_[3], (int)b_[0], (int)b_[1], (int)b_[2], (int)b_[3]};             \
   }
-#endif
   f4 bias;
   if (!STREAM || rounds > 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
       for (int i = 0; i < XT_PIECES; ++i)
-        xt_dma16(W49 + (long)c * XT_CF4 + 4 + i * 64, voff_a, wave_lds + (unsigned)c * 24576u + (unsigned)i * 1024u);
+        xt_dma16_imm<0>(W49 + (long)c * XT_CF4 + 4 + i * 64, voff_a, wave_lds + (unsigned)c * 24576u + (unsigned)i * 1024u);
     asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // chunk 0 landed; chunks 1, 2 stay in flight
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-#if XT_FP8
       wh[k] = ring_u[XT_F16OFF(k, 0)];
       wm[k] = ring_u[XT_F16OFF(k, 1)];
-#else
-      wh[k] = ring_u[(k * 3 + 0) * 64];
-      wm[k] = ring_u[(k * 3 + 1) * 64];
-      wl[k] = ring_u[(k * 3 + 2) * 64];
-#endif
     }
-#if XT_FP8
     XT_LOAD8(w8h, ring_u, 512)
     XT_LOAD8(w8l, ring_u, 640)
-#endif
     bias = bias_tab[g];
   }
 
   unsigned sat = 0u;                   // range sentinel: running max of the h pieces (all >= 0 here: ReLU outputs)
-#if XT_FP8
   struct Ops {
     u4 h[2][8], m[2][8];               // B operands of a layer, two tiles: the f16 h and m pieces (one 128-bit tuple per k-block)
     xt_i8 h8[2][2], l8[2][2];          // ... and bf8 copies of the h and l pieces, 32 K values per lane and half (the top bytes of the f16 pieces)
   };
   unsigned el_keep[2] = {0u, 0u};
-#else
-  struct Ops {
-    u4 h[2][8], m[2][8], l[2][8];      // B operands of a layer, two tiles (one 128-bit tuple per k-block and piece)
-  };
-#endif
   Ops P, Q;                            // current / next layer's operands, filled chunk by chunk; the layers alternate the roles
 
 #define XT_MFMA(ACC, WREG, XREG) \
@@ -235,16 +207,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
     asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(mu), "s"(negk), "v"(e1));
     Y.h[t][jb >> 1][(jb & 1) * 2 + q] = eh;
     Y.m[t][jb >> 1][(jb & 1) * 2 + q] = mu;
-#if XT_FP8
     if (q == 0) {
       el_keep[t] = lu;
     } else {      // the block's four h and four l halves -> dword jb of the next layer's bf8 operands (their top bytes: e5m2 by truncation)
       Y.h8[t][jb >> 3][jb & 7] = (int)__builtin_amdgcn_perm(eh, Y.h[t][jb >> 1][(jb & 1) * 2], 0x07050301u);
       Y.l8[t][jb >> 3][jb & 7] = (int)__builtin_amdgcn_perm(lu, el_keep[t], 0x07050301u);
     }
-#else
-    Y.l[t][jb >> 1][(jb & 1) * 2 + q] = lu;
-#endif
   };
   // the twelve stage instances of a chunk's epilogue in issue order
   auto ep_slot = [&](Ops& Y, int s, int pj) {
@@ -302,8 +270,8 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const long prow = tpn[t] < 0 ? 0L : (long)tpn[t];
-        xt_dma16(reinterpret_cast<const f4*>(A + prow * 256), (unsigned)lane * 16u,
-                 arow_b + (unsigned)(parity_next * 8 + wave * 2 + t) * 1024u);
+        xt_dma16_imm<0>(reinterpret_cast<const f4*>(A + prow * 256), (unsigned)lane * 16u,
+                        arow_b + (unsigned)(parity_next * 8 + wave * 2 + t) * 1024u);
       }
     }
 #pragma unroll
@@ -435,16 +403,12 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           sx_split_pair(fmaxf(av[2 * q] + bv[2 * q], 0.f), fmaxf(av[2 * q + 1] + bv[2 * q + 1], 0.f), negk, h, m, l);
           P.h[t][kb / 2][(kb & 1) * 2 + q] = h;
           P.m[t][kb / 2][(kb & 1) * 2 + q] = m;
-#if XT_FP8
           if (q == 0) {
             el_keep[t] = l;
           } else {
             P.h8[t][kb >> 3][kb & 7] = (int)__builtin_amdgcn_perm(h, P.h[t][kb / 2][(kb & 1) * 2], 0x07050301u);
             P.l8[t][kb >> 3][kb & 7] = (int)__builtin_amdgcn_perm(l, el_keep[t], 0x07050301u);
           }
-#else
-          P.l[t][kb / 2][(kb & 1) * 2 + q] = l;
-#endif
           sat = sat_acc_nonneg(sat, h);
         }
       }
@@ -486,11 +450,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #ifdef XT_ABL_NOLDS                   // timing ablation (wrong results): no fragment reads
 #define XT_FRAG(DST, KB, PIECE) asm volatile("" : "+v"(DST))
 #else
-#if XT_FP8
 #define XT_FRAG(DST, KB, PIECE) DST = nfrag[XT_F16OFF(KB, PIECE)]
-#else
-#define XT_FRAG(DST, KB, PIECE) DST = nfrag[((KB) * 3 + (PIECE)) * 64]
-#endif
 #endif
 #define XT_MFMA8(ACC, WREG, XREG) ACC = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(WREG, XREG, ACC, 1, 1, 0, 0, 0, 0)
 #define XT_EP(S)                        \
@@ -523,7 +483,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
               acc[t].c1 = acc[t].c2 = f4{0.f, 0.f, 0.f, 0.f};
             }
           }
-#if XT_FP8
           if constexpr (NT == 1) {
             // tile 0's six positions (1, 2, 3, 7, 8, 11 of the two-tile body); the fragments' last use is here, so the refills follow
             // them; a first half carries tile 0's six epilogue stages, the copies go one behind each position
@@ -551,16 +510,13 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #endif
             if (H == 0) XT_EP(7); else XT_COPY(5);
             XT_FENCE;
-          } else
-#endif
-          {
+          } else {
           XT_RUN(acc[0].c0, wh, X.h[0]);                       // 1
           if (H == 0) XT_EP(0); else XT_EP(9);
           XT_FENCE;
           XT_RUN(acc[0].c1, wh, X.m[0]);                       // 2
           if (H == 0) XT_EP(1); else XT_EP(10);
           XT_FENCE;
-#if XT_FP8
           XT_MFMA8(acc[0].c2, w8h, X.l8[0][H]);                // 3: h.xl of the half's 128 K as ONE bf8 MFMA
           if (H == 0) XT_EP(2); else XT_EP(11);
           XT_FENCE;
@@ -578,19 +534,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
 #endif
           if (H == 0) XT_EP(4); else XT_COPY(1);
           XT_FENCE;
-#else
-          XT_RUN(acc[0].c2, wh, X.l[0]);                       // 3
-          if (H == 0) XT_EP(2); else XT_EP(11);
-          XT_FENCE;
-          XT_RUN(acc[1].c0, wh, X.h[1]);                       // 4
-          if (H == 0) XT_EP(3); else XT_COPY(0);
-          XT_FENCE;
-          XT_RUN(acc[1].c1, wh, X.m[1]);                       // 5
-          if (H == 0) XT_EP(4); else XT_COPY(1);
-          XT_FENCE;
-          XT_RUN_REFILL(acc[1].c2, wh, X.l[1], 0);             // 6: the h fragments' last use
-          XT_FENCE;
-#endif
           XT_RUN(acc[0].c1, wm, X.h[0]);                       // 7
           if (H == 0) XT_EP(5); else XT_COPY(2);
           XT_FENCE;
@@ -602,7 +545,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           XT_FENCE;
           XT_RUN_REFILL(acc[1].c2, wm, X.m[1], 1);             // 10: the m fragments' last use
           XT_FENCE;
-#if XT_FP8
           XT_MFMA8(acc[0].c2, w8l, X.h8[0][H]);                // 11: l.xh as one bf8 MFMA
           if (H == 0) XT_EP(8); else XT_COPY(5);
           XT_FENCE;
@@ -611,13 +553,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           XT_LOAD8(w8l, nfrag, (1 - H) * 768 + 640)
 #endif
           XT_FENCE;
-#else
-          XT_RUN(acc[0].c2, wl, X.h[0]);                       // 11
-          if (H == 0) XT_EP(8); else XT_COPY(5);
-          XT_FENCE;
-          XT_RUN_REFILL(acc[1].c2, wl, X.h[1], 2);             // 12: the l fragments' last use
-          XT_FENCE;
-#endif
           }
         }
 #undef XT_RUN
@@ -646,11 +581,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         for (int kb = 0; kb < 8; ++kb) {
           P.h[t][kb] = Q.h[t][kb];
           P.m[t][kb] = Q.m[t][kb];
-#if !XT_FP8
-          P.l[t][kb] = Q.l[t][kb];
-#endif
         }
-#if XT_FP8
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -658,7 +589,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           P.h8[t][hf] = Q.h8[t][hf];
           P.l8[t][hf] = Q.l8[t][hf];
         }
-#endif
     }
     // ---- head: chunk 48 from its resident LDS copy; `bias` holds its bias (fetched by the last chunk of layer 2) and the fragment
     // window already holds the first half of the next round's chunk 0.  Next round's rows are requested first: they arrive under
@@ -676,7 +606,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         acc[t].c2 = f4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
-#if XT_FP8
       for (int kb = 0; kb < 8; ++kb) {
         const u4 fh = hw[XT_F16OFF(kb, 0)], fm = hw[XT_F16OFF(kb, 1)];
 #pragma unroll
@@ -698,20 +627,6 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
           acc[t].c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(f8l, P.h8[t][hf], acc[t].c2, 1, 1, 0, 0, 0, 0);
         }
       }
-#else
-      for (int kb = 0; kb < 8; ++kb) {
-        const u4 fh = hw[(kb * 3 + 0) * 64], fm = hw[(kb * 3 + 1) * 64], fl = hw[(kb * 3 + 2) * 64];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          XT_MFMA(acc[t].c0, fh, P.h[t][kb]);
-          XT_MFMA(acc[t].c1, fh, P.m[t][kb]);
-          XT_MFMA(acc[t].c2, fh, P.l[t][kb]);
-          XT_MFMA(acc[t].c1, fm, P.h[t][kb]);
-          XT_MFMA(acc[t].c2, fm, P.m[t][kb]);
-          XT_MFMA(acc[t].c2, fl, P.h[t][kb]);
-        }
-      }
-#endif
       bias = bias_tab[g];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -737,7 +652,7 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         XT_PT(0)
       }
       // the stream form's rounds stay two-tile: only the last round of a launch could be one-tile there
-      const bool tail1 = !STREAM && XT_FP8 && rounds > 0 && S - (rounds - 1) * 128 <= 64;     // workgroup-uniform
+      const bool tail1 = !STREAM && rounds > 0 && S - (rounds - 1) * 128 <= 64;     // workgroup-uniform
       const long rd_end2 = tail1 ? rd_end - 1 : rd_end;
       for (; rd < rd_end2; rd += rd_step) {
         if constexpr (STREAM) tile_lookup(rd + rd_step);
@@ -745,17 +660,17 @@ __global__ __launch_bounds__(256, 1) void k_dvis_x6t(const XtArgs a) {
         ++trounds;
 #endif
         XT_T(3)
-        round_body(XtInt<2>{});
+        round_body(std::integral_constant<int, 2>{});
         parity ^= 1;
         XT_T(2)
       }
-      if constexpr (!STREAM && XT_FP8) {
+      if constexpr (!STREAM) {
         if (tail1) {
 #ifdef XT_TIMING
           ++trounds;
 #endif
           XT_T(3)
-          round_body(XtInt<1>{});
+          round_body(std::integral_constant<int, 1>{});
           XT_T(2)
         }
       }
@@ -826,11 +741,7 @@ extern "C" int rb_dvis_fused_x6t(const float* normals, const int* chunk_id, long
   RB_REQUIRE(normals && A && Bd && dirs && wdir && wsum && W49 && vis_out, "null pointer");
   RB_REQUIRE(n <= RB_MAX_BLOCKS, "too many points for one launch (one workgroup each)");
   RB_REQUIRE(L > 0 && L <= 256 && nsamp > 0 && (long)L * nsamp <= DVIS_MAX_DIRS, "need L <= 256 and L*nsamp <= 4096");
-#if XT_FP8
   RB_REQUIRE(scale_log2 == 8, "this build of k_dvis_x6t takes the bf8 weight layout (packing.repack_x6_chunks_fp8; scale_log2 = 8 names it)");
-#else
-  RB_REQUIRE(scale_log2 == 0, "k_dvis_x6t takes weights packed with scale_log2 = 0");
-#endif
   XtArgs a{};
   a.A = A, a.Bd = Bd, a.W49 = (const f4*)W49, a.argmax_vis = argmax_vis;
   a.range_word = range_flags() ? range_flags() + RB_RANGE_DVIS : nullptr;
@@ -850,12 +761,8 @@ extern "C" int rb_dvis_stream_x6(const float* normals, const int* chunk_id, long
                                  int argmax_vis, int scale_log2, unsigned short* pair_j, float* pair_vis, int* tile_info,
                                  int* point_info, unsigned long long* counters, int n_workgroups, float* vis_out,
                                  unsigned long long* eval_count, rb_stream_t stream) {
-#if XT_FP8
   const char* const format_error =
       scale_log2 == 8 ? nullptr : "this build of k_dvis_x6t takes the bf8 weight layout (packing.repack_x6_chunks_fp8; scale_log2 = 8 names it)";
-#else
-  const char* const format_error = scale_log2 == 0 ? nullptr : "k_dvis_x6t takes weights packed with scale_log2 = 0";
-#endif
   return dvis_tile_list_launch(__func__, format_error, "k_dvis_x6t<stream>", normals, chunk_id, n, A, Bd, dirs, wdir, wsum, W49, L, nsamp, pair_j,
                                pair_vis, tile_info, point_info, counters, n_workgroups, vis_out, eval_count, stream,
                                [&](const DvisTile* tiles, dim3 grid, hipStream_t s) {

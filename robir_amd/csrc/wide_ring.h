@@ -20,15 +20,8 @@
 namespace rb {
 
 constexpr int WR_SLOT_B = 34 * 1024;          // K = 544: 34 KB of fragments
-#ifndef WR_FD
-#define WR_FD 3
-#endif
-#ifndef WR_BS
-#define WR_BS 2          // k-blocks per batch of fragment reads
-#endif
-#ifndef WR_DB
-#define WR_DB 2          // batches the fragment reads run ahead of the MFMAs
-#endif
+constexpr int WR_BS = 2;                      // k-blocks per batch of fragment reads
+constexpr int WR_DB = 2;                      // batches the fragment reads run ahead of the MFMAs
 
 // ---- net descriptions: K (padded inputs) and chunks (16 output neurons each) per layer
 template <int K0P, int N3P>

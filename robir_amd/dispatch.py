@@ -130,13 +130,14 @@ _DVIS = {       # resolved form: entry point, legacy library, weights and format
     "f16x3-v2": ("rb_dvis_fused_v2", True, *_H3_HEAD, "point"),       # two tiles per wave, one workgroup per CU, head on the matrix pipe (vis_diffuse_v2.hip)
     "f16x3-v3": ("rb_dvis_stream", True, *_H3_HEAD, "stream"),        # global tile list + persistent grid (vis_diffuse_v3.hip)
     "f16x6-1t": ("rb_dvis_fused_x6", True, *_X6_HEAD, "point"),       # round 3's one tile per wave, one workgroup per point (vis_diffuse_x6.hip)
-    "f16x6-pt": ("rb_dvis_fused_x6t", False, *_X6_HEAD, "point"),     # two tiles per wave, one workgroup per point (vis_diffuse_x6t.hip)
-    "f16x6-stream": ("rb_dvis_stream_x6", False, *_X6_HEAD, "stream"),    # ... persistent grid over the global tile list: bit-identical to -pt
+    # two tiles per wave, two of the six products on the bf8 MFMA (vis_diffuse_x6t.hip; format 8 names the bf8 weight layout)
+    "f16x6-pt": ("rb_dvis_fused_x6t", False, "hidden_x6_head_fp8", 8, "point"),       # a persistent grid that takes point after point
+    "f16x6-stream": ("rb_dvis_stream_x6", False, "hidden_x6_head_fp8", 8, "stream"),  # ... over the global tile list: bit-identical to -pt
     "f16x1": ("rb_dvis_stream_f16", False, *_X6_HEAD, "stream")}        # generation 1; 2: format 1 = the h-only blob; 3: the point-block form
 DVIS_FORMS = tuple(_DVIS)
 
 
-def dvis(precision, n, L, nsamp, x6_form, x6_fp8, f16_gen, ascending, stream_max_points=8192, stream_short_list=1024):
+def dvis(precision, n, L, nsamp, x6_form, f16_gen, ascending, stream_max_points=8192, stream_short_list=1024):
     """ops.dvis_fused.  ascending: callable (chunk ids never decrease), asked for 'f16x1' with generation 3 only; stream_max_points /
     stream_short_list: ops.DVIS_STREAM_MAX_POINTS / DVIS_STREAM_SHORT_LIST."""
     check("ROBIR_VIS_PRECISION", precision)
@@ -163,6 +164,4 @@ def dvis(precision, n, L, nsamp, x6_form, x6_fp8, f16_gen, ascending, stream_max
             entry, blob, fmt, layout = "rb_dvis_pblock_f16", "hidden_f16_head", None, "pblock"
         elif f16_gen >= 2:
             blob, fmt = "hidden_f16_head", 1
-    elif x6_fp8 and precision in ("f16x6-pt", "f16x6-stream"):      # the two-tile kernel as built: two of its six products on the bf8 MFMA
-        blob, fmt = "hidden_x6_head_fp8", 8
     return Dvis(precision, entry, legacy, blob, fmt, layout)

@@ -687,7 +687,7 @@ def chunk_ids_ascending(chunk_id):
         known = bool((chunk_id[1:] >= chunk_id[:-1]).all())
         chunk_id._robir_ascending = known
     return known
-DVIS_X6_FP8 = os.environ.get("ROBIR_DVIS_X6_FP8", "1") == "1"      # the two-tile light-visibility kernel as built (csrc/vis_diffuse_x6t.hip XT_FP8 = 1: two of its six products on the bf8 MFMA) takes the weight layout of packing.repack_x6_chunks_fp8; 0 for a library built with -DXT_FP8=0 (a mismatch is refused by the entry point)
+DVIS_X6_FP8 = True      # a constant: k_dvis_x6t forms two of its six products on the bf8 MFMA (bench.py reads this for its roofline bound)
 DVIS_X6_FORM = os.environ.get("ROBIR_DVIS_X6_FORM", "auto")          # what "f16x6" runs: auto | f16x6-pt | f16x6-stream | f16x6-1t
 
 
@@ -698,7 +698,7 @@ def dvis_fused(normals, chunk_id, A, Bd, dirs, wdir, wsum, split, L, nsamp, argm
     f16: NARROWER than fp32).  Which kernel form, weight blob and format serve the call: dispatch.dvis."""
     normals = _f32(normals)
     n, dev = normals.shape[0], normals.device
-    r = dispatch.dvis(precision, n, L, nsamp, DVIS_X6_FORM, DVIS_X6_FP8, DVIS_F16_GEN, lambda: chunk_ids_ascending(chunk_id),
+    r = dispatch.dvis(precision, n, L, nsamp, DVIS_X6_FORM, DVIS_F16_GEN, lambda: chunk_ids_ascending(chunk_id),
                       DVIS_STREAM_MAX_POINTS, DVIS_STREAM_SHORT_LIST)
     out = torch.empty(n, L, dtype=torch.float32, device=dev)
     if chunk_id is not None:

@@ -186,7 +186,7 @@ class _VisSplit(dict):
             v = pack_layers_h3(self._hl + [dict(W=self["w_last"], b=self["b_last"], n_pad=16, k_pad=256)], self._device)
         elif k == "hidden_f16_head":
             v = pack_vis_f16_head(self["hidden_x6_head"])
-        elif k == "hidden_x6_head_fp8":      # the 49 chunks in the bf8 layout (k_dvis_x6t built with -DXT_FP8=1; format 8)
+        elif k == "hidden_x6_head_fp8":      # the 49 chunks in the bf8 layout (k_dvis_x6t; format 8)
             v = repack_x6_chunks_fp8(self["hidden_x6_head"], self._device, ((256, 49),))
         else:
             raise KeyError(k)

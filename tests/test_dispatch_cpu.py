@@ -12,6 +12,7 @@ entry-point calls.
 import itertools
 import json
 import os
+import subprocess
 import sys
 
 import pytest
@@ -146,7 +147,7 @@ def test_table_dvis(golden):
     for case, rec in section(golden, "dvis_fused"):
         asked = []
         args = dict(precision=case["precision"], n=case["n"], L=case["L_nsamp"][0], nsamp=case["L_nsamp"][1], x6_form=case["x6_form"],
-                    x6_fp8=case["x6_fp8"], f16_gen=case["f16_gen"], ascending=lambda: asked.append(1) or case["chunk_ids"] != "descending" or case["n"] < 2)      # what ops.chunk_ids_ascending answers
+                    f16_gen=case["f16_gen"], ascending=lambda: asked.append(1) or case["chunk_ids"] != "descending" or case["n"] < 2)      # what ops.chunk_ids_ascending answers
         if "raises" in rec:
             with pytest.raises(ValueError) as e:
                 dispatch.dvis(**args)
@@ -193,7 +194,7 @@ def test_default_policies_stay_in_the_default_library(golden, policy, cesr):
             assert all(c.fn in ("sdf_points_x6", "sdf_value_grad_x6", "sdf_mlp_points") for c in r.calls)
     vis = precision.POLICIES[policy][0]
     for case, rec in section(golden, "dvis_fused"):
-        if (case["precision"], case["x6_form"], case["x6_fp8"], case["f16_gen"]) == (vis, "auto", True, 3) and "raises" not in rec:
+        if (case["precision"], case["x6_form"], case["f16_gen"]) == (vis, "auto", 3) and "raises" not in rec:
             assert not rec["legacy"], (case, rec)
 
 
@@ -218,12 +219,25 @@ def test_totality():
     with pytest.raises(ValueError, match="ROBIR_CESR_PRECISION must be f16x1, f16x6, fp32 or f16x3"):
         dispatch.cesr("f16x6", "bf16", True, True)
     with pytest.raises(ValueError, match="ROBIR_VIS_PRECISION must be one of"):
-        dispatch.dvis("f16", 1, 128, 32, "auto", True, 3, lambda: True)
+        dispatch.dvis("f16", 1, 128, 32, "auto", 3, lambda: True)
     with pytest.raises(ValueError, match="ROBIR_DVIS_X6_FORM"):
-        dispatch.dvis("f16x6", 1, 128, 32, "f16x6-2t", True, 3, lambda: True)
+        dispatch.dvis("f16x6", 1, 128, 32, "f16x6-2t", 3, lambda: True)
 
 
 def test_dispatch_is_pure():
     """The table imports neither torch nor the library loader."""
     src = open(os.path.join(ROOT, "robir_amd", "dispatch.py")).read()
     assert "import torch" not in src and "_lib" not in src and "import ops" not in src
+
+
+def test_dead_x6_fp8_variable_is_ignored():
+    """ROBIR_DVIS_X6_FP8 once named the build form of k_dvis_x6t; there is one form now, and a fresh interpreter that finds the variable set to
+    0 still routes the two-tile kernel to the bf8 weight layout (format 8)."""
+    code = ("from robir_amd import dispatch, ops\n"
+            "assert ops.DVIS_X6_FP8 is True\n"
+            "r = dispatch.dvis('f16x6', 1, 128, 32, 'auto', 3, lambda: True)\n"
+            "print(r.blob, r.fmt)\n")
+    env = dict(os.environ, ROBIR_DVIS_X6_FP8="0", PYTHONPATH=os.pathsep.join([ROOT] + [p for p in (os.environ.get("PYTHONPATH"),) if p]))
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == ["hidden_x6_head_fp8", "8"]

@@ -33,7 +33,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "dispatch_table.json")
 ENV = ("ROBIR_PRECISION", "ROBIR_MLP_PRECISION", "ROBIR_CESR_PRECISION", "ROBIR_VIS_PRECISION", "ROBIR_RANGE_CHECK")
 OPS_PREFIXES = ("sdf_", "feat_", "color_", "vis_", "wide_", "cesr_", "illum_", "ae_", "linear_")
 OPS_NAMES = ("axpy", "abs_scale", "normalize3", "material_decode")
-OPS_TOGGLES = ("SDF_FUSED_PE", "SDF_KERNEL", "SDF_GRAD", "DVIS_X6_FORM", "DVIS_X6_FP8", "DVIS_F16_GEN")
+OPS_TOGGLES = ("SDF_FUSED_PE", "SDF_KERNEL", "SDF_GRAD", "DVIS_X6_FORM", "DVIS_F16_GEN")
 N_RESULTS = {"sdf_mlp": 2, "sdf_mlp_points": 2, "sdf_mlp_h3": 2, "sdf_points_jvp_h3": 2, "sdf_value_grad": 2, "sdf_value_grad_f32": 2,
              "sdf_value_grad_x6": 2, "ae_latent": 2, "material_decode": 6}
 SPLIT_BLOBS = ("point", "dir", "hidden", "hidden_h3", "hidden_h3_head", "hidden_x6_head", "hidden_x6_head_fp8", "hidden_f16_head", "w_last",
@@ -243,7 +243,7 @@ SDF_AXES = (("mlp", ("fp32", "f16x3", "f16x6")), ("fused_pe", (False, True)), ("
 NETS_AXES = (("policy", tuple(precision.POLICIES)), ("mlp_override", ("", "fp32", "f16x3", "f16x6")), ("cesr_override", ("", "f16x1", "f16x6")),
              ("fused_pe", (False, True)), ("call", tuple(NET_CALLS)))
 DVIS_AXES = (("precision", precision.VIS_MODES), ("n", (1, 8192, 8193)), ("L_nsamp", ((128, 32), (128, 8), (3, 8))),
-             ("x6_form", ("auto", "f16x6-pt", "f16x6-stream", "f16x6-1t")), ("x6_fp8", (False, True)), ("f16_gen", (1, 2, 3)),
+             ("x6_form", ("auto", "f16x6-pt", "f16x6-stream", "f16x6-1t")), ("f16_gen", (1, 2, 3)),
              ("chunk_ids", ("ascending", "descending", "none")))
 
 
@@ -281,7 +281,7 @@ class _Split(dict):
 
 def drive_dvis(rec, m, c):
     n, (L, nsamp) = c["n"], c["L_nsamp"]
-    ops.DVIS_X6_FORM, ops.DVIS_X6_FP8, ops.DVIS_F16_GEN = c["x6_form"], c["x6_fp8"], c["f16_gen"]
+    ops.DVIS_X6_FORM, ops.DVIS_F16_GEN = c["x6_form"], c["f16_gen"]
     chunk_id, C = None, 1
     if c["chunk_ids"] != "none":
         C = 2
