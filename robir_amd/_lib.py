@@ -39,14 +39,18 @@ ILLUMTRAIN_ABI_VERSION = 1
 CESRTRAIN_PATH = os.path.join(_HERE, "librobir_hip_cesrtrain.so")
 _cesrtrain = None
 CESRTRAIN_ABI_VERSION = 1
+LIGHTFIT_PATH = os.path.join(_HERE, "librobir_hip_lightfit.so")
+_lightfit = None
+LIGHTFIT_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
     """Compile every HIP translation unit for gfx950 and link, in-tree, librobir_hip.so (the default library), librobir_hip_train.so (the
     training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/),
     librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/),
-    librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/) and -- legacy=True --
-    librobir_hip_legacy.so (the superset with the retired kernel generations, csrc/Makefile)."""
+    librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
+    the light SGs to an environment map, csrc/lightfit/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
     r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j", jobs, "all" if legacy else "default"],
@@ -180,6 +184,21 @@ def cesrtrain():
 def call_cesrtrain(name, *args):
     """An entry point of the CESR-training library."""
     _call_aux(cesrtrain(), name, *args)
+
+
+def lightfit():
+    """The light-fitting library (include/robir_hip_lightfit.h; `make -C robir_amd/csrc lightfit`): the reverse mode of the SG environment
+    map, the fused steps of the fit and the area down-sample."""
+    global _lightfit
+    if _lightfit is None:
+        _lightfit = _load_aux(LIGHTFIT_PATH, LIGHTFIT_ABI_VERSION, "rb_lf_", ("rb_lf_scratch_bytes", "rb_lf_groups"), "lightfit",
+                              "LIGHT-FITTING library librobir_hip_lightfit.so", "light SGs of an environment map, robir_amd/lightfit.py")
+    return _lightfit
+
+
+def call_lightfit(name, *args):
+    """An entry point of the light-fitting library."""
+    _call_aux(lightfit(), name, *args)
 
 
 def legacy_loaded():
