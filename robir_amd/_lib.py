@@ -42,6 +42,9 @@ CESRTRAIN_ABI_VERSION = 1
 LIGHTFIT_PATH = os.path.join(_HERE, "librobir_hip_lightfit.so")
 _lightfit = None
 LIGHTFIT_ABI_VERSION = 1
+TEXBAKE_PATH = os.path.join(_HERE, "librobir_hip_texbake.so")
+_texbake = None
+TEXBAKE_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -49,7 +52,7 @@ def build(verbose=False, legacy=True):
     training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/),
     librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/),
     librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
-    the light SGs to an environment map, csrc/lightfit/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -199,6 +202,21 @@ def lightfit():
 def call_lightfit(name, *args):
     """An entry point of the light-fitting library."""
     _call_aux(lightfit(), name, *args)
+
+
+def texbake():
+    """The texture-baking library (include/robir_hip_texbake.h; `make -C robir_amd/csrc texbake`): the per-triangle UV atlas, the UV-space
+    rasteriser, attribute interpolation, border dilation and the surface sampler."""
+    global _texbake
+    if _texbake is None:
+        _texbake = _load_aux(TEXBAKE_PATH, TEXBAKE_ABI_VERSION, "rb_tb_", ("rb_tb_atlas_cell",), "texbake",
+                             "TEXTURE-BAKING library librobir_hip_texbake.so", "material textures of an extracted mesh, robir_amd/texture.py")
+    return _texbake
+
+
+def call_texbake(name, *args):
+    """An entry point of the texture-baking library."""
+    _call_aux(texbake(), name, *args)
 
 
 def legacy_loaded():

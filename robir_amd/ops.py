@@ -1474,3 +1474,102 @@ def mesh_block_fill(blocks, B, vals, field):
     nx, ny, nz = field.shape
     call("rb_mesh_block_fill", ptr(blocks), c_long(blocks.numel()), c_int(B), ptr(vals), c_int(nx), c_int(ny), c_int(nz), ptr(field),
          stream_ptr())
+
+
+# ----------------------------------------------------------------------------------------- texture space (csrc/texbake/texbake.hip)
+TB_TILE, TB_MAX_RESOLUTION = 8, 16384
+
+
+def _tb_uv(uv):
+    uv = _f32(uv)
+    if uv.dim() != 3 or tuple(uv.shape[1:]) != (3, 2):
+        raise ValueError(f"texture space: uv must be [F,3,2] per face corner, got {tuple(uv.shape)}")
+    return uv
+
+
+def tb_atlas_cell(n_faces, resolution):
+    """Cell size S of the per-triangle atlas; ValueError (naming the smallest resolution that works) below S = 6."""
+    L = _lib.texbake()
+    S = L.rb_tb_atlas_cell(c_long(int(n_faces)), c_int(int(resolution)))
+    if S < 0:
+        raise ValueError("atlas_uv: " + _lib.aux_error(L))
+    return int(S)
+
+
+def tb_atlas_uv(n_faces, resolution, device):
+    tb_atlas_cell(n_faces, resolution)
+    uv = torch.empty(int(n_faces), 3, 2, dtype=torch.float32, device=device)
+    _lib.call_texbake("rb_tb_atlas_uv", c_long(int(n_faces)), c_int(int(resolution)), ptr(uv), stream_ptr())
+    return uv
+
+
+def tb_bin_count(uv, R):
+    """uv [F,3,2] -> counts [F] int32: tiles of 8 x 8 texels each face's texel box touches."""
+    uv = _tb_uv(uv)
+    counts = torch.empty(uv.shape[0], dtype=torch.int32, device=uv.device)
+    _lib.call_texbake("rb_tb_bin_count", ptr(uv), c_long(uv.shape[0]), c_int(R), ptr(counts), stream_ptr())
+    return counts
+
+
+def tb_bin_emit(uv, R, base, P):
+    """base [F] int64 exclusive prefix of the counts, P their total -> (pair_tile [P], pair_face [P]) int32 in face order."""
+    uv = _tb_uv(uv)
+    assert base.dtype == torch.int64 and base.numel() == uv.shape[0]
+    pair_tile = torch.empty(P, dtype=torch.int32, device=uv.device)
+    pair_face = torch.empty(P, dtype=torch.int32, device=uv.device)
+    _lib.call_texbake("rb_tb_bin_emit", ptr(uv), c_long(uv.shape[0]), c_int(R), ptr(base), c_long(P), ptr(pair_tile), ptr(pair_face), stream_ptr())
+    return pair_tile, pair_face
+
+
+def tb_raster(uv, R, tile_start, pair_face):
+    """-> (face_id [R,R] int32, bary [R,R,2])."""
+    uv = _tb_uv(uv)
+    ntiles = (R + TB_TILE - 1) // TB_TILE
+    assert tile_start.dtype == torch.int32 and tile_start.numel() == ntiles * ntiles + 1 and pair_face.dtype == torch.int32
+    face_id = torch.empty(R, R, dtype=torch.int32, device=uv.device)
+    bary = torch.empty(R, R, 2, dtype=torch.float32, device=uv.device)
+    P = pair_face.numel()
+    _lib.call_texbake("rb_tb_raster", ptr(uv) if uv.numel() else None, c_long(uv.shape[0]), c_int(R), ptr(tile_start),
+                      ptr(pair_face) if P else None, c_long(P), ptr(face_id), ptr(bary), stream_ptr())
+    return face_id, bary
+
+
+def tb_interp(face_id, bary, faces, attr, index=None):
+    """attr [V,C] at the texels of face_id / bary -> [R,R,C] (index None) or [n,C] at the flat texel indices index [n] int64."""
+    assert face_id.dtype == torch.int32 and face_id.is_contiguous() and faces.dtype == torch.int32
+    bary, attr, faces = _f32(bary), _f32(attr), faces.contiguous()
+    if attr.dim() != 2 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"interpolate: attr must be [V,C] and faces [F,3], got {tuple(attr.shape)}, {tuple(faces.shape)}")
+    T, C = face_id.numel(), attr.shape[1]
+    if index is None:
+        n, out = T, torch.empty(*face_id.shape, C, dtype=torch.float32, device=face_id.device)
+    else:
+        assert index.dtype == torch.int64 and index.is_contiguous()
+        n, out = index.numel(), torch.empty(index.numel(), C, dtype=torch.float32, device=face_id.device)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_texbake("rb_tb_interp", ptr(face_id), ptr(bary), c_long(T), None if index is None else nz(index), c_long(n), nz(faces),
+                      c_long(faces.shape[0]), nz(attr), c_long(attr.shape[0]), c_int(C), nz(out), stream_ptr())
+    return out
+
+
+def tb_dilate(image, mask):
+    """One ring: image [H,W,C], mask [H,W] uint8 -> (image', mask') in new tensors."""
+    image = _f32(image)
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and image.dim() == 3 and tuple(mask.shape) == tuple(image.shape[:2])
+    H, W, C = image.shape
+    dst, mask_out = torch.empty_like(image), torch.empty_like(mask)
+    _lib.call_texbake("rb_tb_dilate", ptr(image), ptr(mask), c_int(H), c_int(W), c_int(C), ptr(dst), ptr(mask_out), stream_ptr())
+    return dst, mask_out
+
+
+def tb_sample(position, normal, mask, uv, scale):
+    """position, normal [R,R,3], mask [R,R], uv [n,2] -> x, normal, object_mask (uint8), tangent_u, tangent_v."""
+    position, normal, mask, uv = _f32(position), _f32(normal), _f32(mask), _f32(uv)
+    R, n, dev = position.shape[0], uv.shape[0], position.device
+    assert tuple(position.shape) == (R, R, 3) and tuple(normal.shape) == (R, R, 3) and tuple(mask.shape) == (R, R) and tuple(uv.shape) == (n, 2)
+    x, nrm, tu, tv = (torch.empty(n, 3, dtype=torch.float32, device=dev) for _ in range(4))
+    om = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n:
+        _lib.call_texbake("rb_tb_sample", ptr(position), ptr(normal), ptr(mask), c_int(R), ptr(uv), c_long(n), c_float(scale), ptr(x), ptr(nrm),
+                          ptr(om), ptr(tu), ptr(tv), stream_ptr())
+    return x, nrm, om, tu, tv
