@@ -45,6 +45,9 @@ LIGHTFIT_ABI_VERSION = 1
 TEXBAKE_PATH = os.path.join(_HERE, "librobir_hip_texbake.so")
 _texbake = None
 TEXBAKE_ABI_VERSION = 1
+OBSERVE_PATH = os.path.join(_HERE, "librobir_hip_observe.so")
+_observe = None
+OBSERVE_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -52,7 +55,8 @@ def build(verbose=False, legacy=True):
     training-side kernels, csrc/train/), librobir_hip_vistrain.so (the visibility network's backward, csrc/vistrain/),
     librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/),
     librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
-    the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/),
+    librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -217,6 +221,21 @@ def texbake():
 def call_texbake(name, *args):
     """An entry point of the texture-baking library."""
     _call_aux(texbake(), name, *args)
+
+
+def observe():
+    """The observation library (include/robir_hip_observe.h; `make -C robir_amd/csrc observe`): the inverse projection of surface points into
+    the training views with its colour and mask fetch, the choice of n_obs views per point and the fused weighted colour statistics."""
+    global _observe
+    if _observe is None:
+        _observe = _load_aux(OBSERVE_PATH, OBSERVE_ABI_VERSION, "rb_ob_", (), "observe",
+                             "OBSERVATION library librobir_hip_observe.so", "multi-view observations of surface points, robir_amd/observe.py")
+    return _observe
+
+
+def call_observe(name, *args):
+    """An entry point of the observation library."""
+    _call_aux(observe(), name, *args)
 
 
 def legacy_loaded():

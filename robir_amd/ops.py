@@ -1573,3 +1573,114 @@ def tb_sample(position, normal, mask, uv, scale):
         _lib.call_texbake("rb_tb_sample", ptr(position), ptr(normal), ptr(mask), c_int(R), ptr(uv), c_long(n), c_float(scale), ptr(x), ptr(nrm),
                           ptr(om), ptr(tu), ptr(tv), stream_ptr())
     return x, nrm, om, tu, tv
+
+
+# ----------------------------------------------------------------------------------------- observations (csrc/observe/observe.hip)
+OB_MAX_CAMERAS, OB_MAX_OBS = 4096, 8
+
+
+def _ob_cameras(cam_loc, pose_inv, K):
+    cam_loc, pose_inv, K = _f32(cam_loc), _f32(pose_inv), _f32(K)
+    M = cam_loc.shape[0]
+    if tuple(cam_loc.shape) != (M, 3) or tuple(pose_inv.shape) != (M, 4, 4) or tuple(K.shape) != (M, 3, 3):
+        raise ValueError(f"observations: cam_loc [M,3], pose_inv [M,4,4], intrinsics [M,3,3], got {tuple(cam_loc.shape)}, "
+                         f"{tuple(pose_inv.shape)}, {tuple(K.shape)}")
+    return cam_loc, pose_inv, K, M
+
+
+def _ob_images(images, M):
+    images = _f32(images)
+    if images.dim() != 4 or images.shape[0] != M:
+        raise ValueError(f"observations: images must be [M,H,W,C] for M = {M} cameras, got {tuple(images.shape)}")
+    return images
+
+
+def ob_scatter(x, cam_loc, pose_inv, K, images, masks=None):
+    """x [N,3]; cam_loc [M,3], pose_inv [M,4,4], K [M,3,3]; images [M,H,W,C], masks [M,H,W] or None -> uv [M,N,2], view_dir [M,N,3],
+    rgb [M,N,C], valid [M,N] uint8."""
+    x = _f32(x)
+    cam_loc, pose_inv, K, M = _ob_cameras(cam_loc, pose_inv, K)
+    images = _ob_images(images, M)
+    _, H, W, C = images.shape
+    if masks is not None:
+        masks = _f32(masks)
+        if tuple(masks.shape) != (M, H, W):
+            raise ValueError(f"observations: masks must be [M,H,W] = {(M, H, W)}, got {tuple(masks.shape)}")
+    N, dev = x.shape[0], x.device
+    assert tuple(x.shape) == (N, 3)
+    uv = torch.empty(M, N, 2, dtype=torch.float32, device=dev)
+    view_dir = torch.empty(M, N, 3, dtype=torch.float32, device=dev)
+    rgb = torch.empty(M, N, C, dtype=torch.float32, device=dev)
+    valid = torch.empty(M, N, dtype=torch.uint8, device=dev)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_observe("rb_ob_scatter", nz(x), c_long(N), ptr(cam_loc), ptr(pose_inv), ptr(K), c_int(M), ptr(images),
+                      None if masks is None else ptr(masks), c_int(H), c_int(W), c_int(C), nz(uv), nz(view_dir), nz(rgb), nz(valid), stream_ptr())
+    return uv, view_dir, rgb, valid
+
+
+def ob_select(vis, draws, n_obs):
+    """vis [M,N] uint8, draws [M,N] -> (index [n_obs,N] int32: the cameras of the n_obs largest keys vis + 0.01 draws, count [N] int32)."""
+    draws = _f32(draws)
+    assert vis.dtype == torch.uint8 and vis.is_contiguous() and vis.dim() == 2 and tuple(draws.shape) == tuple(vis.shape)
+    M, N = vis.shape
+    index = torch.empty(int(n_obs), N, dtype=torch.int32, device=vis.device)
+    count = torch.empty(N, dtype=torch.int32, device=vis.device)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_observe("rb_ob_select", nz(vis), nz(draws), c_int(M), c_long(N), c_int(int(n_obs)), nz(index), nz(count), stream_ptr())
+    return index, count
+
+
+def ob_accumulate(x, normals, cam_loc, pose_inv, K, images, vis):
+    """x, normals [N,3]; vis [M,N] uint8 -> (weight [N], mean [N,C], var [N,C], count [N] int32) of the colours the visible cameras see,
+    weighted by max(-n . view_dir, 0)."""
+    x, normals = _f32(x), _f32(normals)
+    cam_loc, pose_inv, K, M = _ob_cameras(cam_loc, pose_inv, K)
+    images = _ob_images(images, M)
+    _, H, W, C = images.shape
+    N, dev = x.shape[0], x.device
+    assert tuple(x.shape) == (N, 3) and tuple(normals.shape) == (N, 3)
+    assert vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (M, N)
+    weight = torch.empty(N, dtype=torch.float32, device=dev)
+    mean = torch.empty(N, C, dtype=torch.float32, device=dev)
+    var = torch.empty(N, C, dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_observe("rb_ob_accumulate", nz(x), nz(normals), c_long(N), ptr(cam_loc), ptr(pose_inv), ptr(K), c_int(M), ptr(images), c_int(H),
+                      c_int(W), c_int(C), nz(vis), nz(weight), nz(mean), nz(var), nz(count), stream_ptr())
+    return weight, mean, var, count
+
+
+def ob_fetch(images, uv):
+    """images [M,H,W,C], uv [M,N,2] pixel positions -> [M,N,C]: grid_sample(align_corners=True, zeros padding) per camera."""
+    uv = _f32(uv)
+    images = _ob_images(images, uv.shape[0])
+    M, H, W, C = images.shape
+    N = uv.shape[1]
+    assert tuple(uv.shape) == (M, N, 2)
+    out = torch.empty(M, N, C, dtype=torch.float32, device=images.device)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_observe("rb_ob_fetch", ptr(images), c_int(M), c_int(H), c_int(W), c_int(C), nz(uv), c_long(N), nz(out), stream_ptr())
+    return out
+
+
+def ob_gather(index, x, cam_loc, pose_inv, K, images, masks=None):
+    """ob_scatter for the pairs (index[k][n], n) only: index [n_obs,N] int32 -> uv [n_obs,N,2], view_dir [n_obs,N,3], rgb [n_obs,N,C],
+    valid [n_obs,N] uint8; zeros where the index is negative."""
+    x = _f32(x)
+    cam_loc, pose_inv, K, M = _ob_cameras(cam_loc, pose_inv, K)
+    images = _ob_images(images, M)
+    _, H, W, C = images.shape
+    if masks is not None:
+        masks = _f32(masks)
+        assert tuple(masks.shape) == (M, H, W)
+    N, dev = x.shape[0], x.device
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 2 and index.shape[1] == N and tuple(x.shape) == (N, 3)
+    n_obs = index.shape[0]
+    uv = torch.empty(n_obs, N, 2, dtype=torch.float32, device=dev)
+    view_dir = torch.empty(n_obs, N, 3, dtype=torch.float32, device=dev)
+    rgb = torch.empty(n_obs, N, C, dtype=torch.float32, device=dev)
+    valid = torch.empty(n_obs, N, dtype=torch.uint8, device=dev)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_observe("rb_ob_gather", nz(index), c_int(n_obs), nz(x), c_long(N), ptr(cam_loc), ptr(pose_inv), ptr(K), c_int(M), ptr(images),
+                      None if masks is None else ptr(masks), c_int(H), c_int(W), c_int(C), nz(uv), nz(view_dir), nz(rgb), nz(valid), stream_ptr())
+    return uv, view_dir, rgb, valid

@@ -9,6 +9,7 @@ eval mode.
 
     python -m robir_amd.texture --synthetic [--scene nonconvex] --mesh-resolution 256 --resolution 4096 --out DIR
     python -m robir_amd.texture --neus-ckpt logs/.../200000.tar [--stage-ckpt exps/.../latest.pth] [--obj user.obj] --out DIR
+    ... --views views.npz        also bakes what the training views observe (observed.png; robir_amd/observe.py)
 
 Conventions: images are [R,R,C] with row 0 at the top; a UV pair is in OBJ convention (v up): texel space is x = u R, y = (1 - v) R.
 """
@@ -26,6 +27,8 @@ from . import ops
 
 CHUNK = 1 << 18
 FILES = ("mesh.obj", "mesh.mtl", "albedo.png", "roughness.png", "metallic.png", "normal.png", "maps.npz")
+OBSERVED_FILE = "observed.png"          # written next to FILES once bake_observations has run
+OBSERVED_PLANES = ("observed", "observed_var", "observed_count")
 
 
 # ----------------------------------------------------------------------------------------- atlas, rasteriser, interpolation, dilation
@@ -94,11 +97,14 @@ def dilate(image, mask, rings=1):
 class TextureSet:
     """The baked planes, float32 on the device: albedo [R,R,3], roughness [R,R], metallic [R,R], normal [R,R,3] (unit SDF gradient, object
     space), position [R,R,3], all dilated `rings` times; mask [R,R] (1 where a face covers the texel centre, before dilation); face_id
-    [R,R] int32; uv [F,3,2] and the mesh they belong to."""
+    [R,R] int32; uv [F,3,2] and the mesh they belong to.  After bake_observations also observed [R,R,3] (the mean colour the training views
+    see), observed_var [R,R,3] and observed_count [R,R] (the number of contributing views), dilated like the others."""
 
     def __init__(self, mesh, uv, face_id, bary, albedo, roughness, metallic, normal, position, mask):
         self.mesh, self.uv, self.face_id, self.bary = mesh, uv, face_id, bary
         self.albedo, self.roughness, self.metallic, self.normal, self.position, self.mask = albedo, roughness, metallic, normal, position, mask
+        self.observed = self.observed_var = self.observed_count = None
+        self.rings = 4
         self.stats = {}
 
     @property
@@ -112,11 +118,45 @@ class TextureSet:
         """A TexSampler on the baked position and normal with the mask grown by one ring, the reference's composition."""
         return TexSampler(self.position, self.normal, dilate(self.mask, self.mask, 1)[1].float(), scale)
 
+    def observed_planes(self):
+        """The planes of bake_observations; empty before it has run."""
+        return {k: getattr(self, k) for k in OBSERVED_PLANES if getattr(self, k) is not None}
+
+    def bake_observations(self, model, focus, rings=None, chunk=None):
+        """Adds the planes observed, observed_var [R,R,3] and observed_count [R,R]: at every covered texel, the mean and the variance of the
+        colours that the training views of `focus` (robir_amd.observe.FocusSampler) see at the texel's baked position, weighted by
+        max(-n . view_dir, 0) with the baked normal, over the views that model.octree_ray_tracer finds unoccluded
+        (robir_amd.observe.observed_color); dilated `rings` times (default: as many as the bake's other planes).  -> self."""
+        from . import observe
+        R = self.resolution
+        rings = self.rings if rings is None else int(rings)
+        covered = self.mask.reshape(-1) > 0
+        idx = torch.nonzero(covered).reshape(-1)
+        dev = self.position.device
+        with torch.no_grad():
+            x, n = self.position.reshape(-1, 3)[idx].contiguous(), self.normal.reshape(-1, 3)[idx].contiguous()
+            mean, var, _, count = observe.observed_color(model, focus, x, n, chunk=chunk)
+            planes = {"observed": torch.zeros(R * R, 3, device=dev), "observed_var": torch.zeros(R * R, 3, device=dev),
+                      "observed_count": torch.zeros(R * R, 1, device=dev)}
+            planes["observed"][idx], planes["observed_var"][idx], planes["observed_count"][idx] = mean, var, count.float()[:, None]
+            mask8 = covered.reshape(R, R).to(torch.uint8)
+            for k, v in planes.items():
+                img = dilate(v.reshape(R, R, -1), mask8, rings)[0]
+                setattr(self, k, img[..., 0].contiguous() if img.shape[-1] == 1 else img)
+        self.stats["observed_fraction"] = float((count > 0).float().mean()) if idx.numel() else 0.0
+        return self
+
     def export(self, out_dir):
         """mesh.obj (v / vn / vt / f v/vt/vn), mesh.mtl, albedo.png (sRGB), roughness.png, metallic.png, normal.png (n 0.5 + 0.5; linear) and
-        maps.npz (the float planes, face_id and uv, lossless) -> the list of paths."""
+        maps.npz (the float planes, face_id and uv, lossless) -> the list of paths.  After bake_observations also observed.png (sRGB), and
+        maps.npz holds the three observed planes too; without it nothing else is written and nothing differs."""
         os.makedirs(out_dir, exist_ok=True)
         p = {k: v.detach().cpu().numpy() for k, v in self.planes().items()}
+        extra = []
+        if self.observed is not None:
+            p.update({k: v.detach().cpu().numpy() for k, v in self.observed_planes().items()})
+            save_png(os.path.join(out_dir, OBSERVED_FILE), _mesh._srgb(p["observed"].astype(np.float64)))
+            extra = [OBSERVED_FILE]
         save_png(os.path.join(out_dir, "albedo.png"), _mesh._srgb(p["albedo"].astype(np.float64)))
         save_png(os.path.join(out_dir, "roughness.png"), p["roughness"])
         save_png(os.path.join(out_dir, "metallic.png"), p["metallic"])
@@ -126,7 +166,7 @@ class TextureSet:
         with open(os.path.join(out_dir, "mesh.mtl"), "w") as f:
             f.write("# robir_amd.texture\nnewmtl baked\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nillum 2\nmap_Kd albedo.png\nmap_Pr roughness.png\n"
                     "map_Pm metallic.png\n# object-space normal map (n * 0.5 + 0.5, linear): normal.png\n")
-        return [os.path.join(out_dir, n) for n in FILES]
+        return [os.path.join(out_dir, n) for n in FILES + tuple(extra)]
 
 
 def _newton_step(src, x, f, g, halvings=4):
@@ -203,6 +243,7 @@ def bake(model, mesh, resolution=2048, project=1, rings=4, uv=None):
         sync()
         t3 = time.perf_counter()
     ts = TextureSet(mesh, uv, face_id, bary, mask=mask8.float(), **out)
+    ts.rings = int(rings)
     ncols = int(np.ceil(np.sqrt((F + 1) // 2))) if F else 0
     ts.stats = {"covered_fraction": idx.numel() / float(R * R), "cell": R // ncols if ncols else 0, "raster_s": t1 - t0, "bake_s": t2 - t1,
                 "dilate_s": t3 - t2}
@@ -321,6 +362,8 @@ def main(argv=None):
     ap.add_argument("--resolution", type=int, default=4096, help="texels per side")
     ap.add_argument("--project", type=int, default=1, help="Newton steps of every texel's point onto the SDF's zero set")
     ap.add_argument("--rings", type=int, default=4, help="dilation rings over the chart borders")
+    ap.add_argument("--views", help="an .npz with images [M,H,W,3], masks [M,H,W] (may be empty), poses [M,4,4] camera-to-world and intrinsics "
+                                    "[M,3,3]: also bake the colour these views observe (" + OBSERVED_FILE + ")")
     ap.add_argument("--out", required=True, help="directory of " + ", ".join(FILES))
     a = ap.parse_args(argv)
     if not a.synthetic and not a.neus_ckpt:
@@ -328,7 +371,7 @@ def main(argv=None):
     from . import renderer
     dev = torch.device("cuda:0")
     if a.synthetic:
-        model = renderer.build_synthetic_model(dev, build_octrees=False, scene=a.scene)
+        model = renderer.build_synthetic_model(dev, build_octrees=bool(a.views), scene=a.scene)
     else:
         import warnings
         with warnings.catch_warnings():          # the NeuS checkpoint is loaded explicitly on the next lines
@@ -354,6 +397,17 @@ def main(argv=None):
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
     ts = bake(model, m, a.resolution, a.project, a.rings, uv)
+    if a.views:
+        from . import observe
+        z = np.load(a.views)
+        missing = [k for k in ("images", "masks", "poses", "intrinsics") if k not in z]
+        if missing:
+            ap.error(f"{a.views} lacks the arrays {missing}")
+        if model.octree_ray_tracer.sdf_octree is None:
+            model.octree_ray_tracer.generate(None)
+        as_dev = lambda k: torch.from_numpy(np.ascontiguousarray(z[k], dtype=np.float32)).to(dev)
+        ts.bake_observations(model, observe.FocusSampler(as_dev("images"), as_dev("masks"), as_dev("poses"), as_dev("intrinsics")))
+        torch.cuda.synchronize(dev)
     t2 = time.perf_counter()
     ts.export(a.out)
     t3 = time.perf_counter()
