@@ -48,6 +48,9 @@ TEXBAKE_ABI_VERSION = 1
 OBSERVE_PATH = os.path.join(_HERE, "librobir_hip_observe.so")
 _observe = None
 OBSERVE_ABI_VERSION = 1
+PHOTOLOSS_PATH = os.path.join(_HERE, "librobir_hip_photoloss.so")
+_photoloss = None
+PHOTOLOSS_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -56,7 +59,8 @@ def build(verbose=False, legacy=True):
     librobir_hip_illumtrain.so (the indirect-illumination lobe net's backward and the fused SG query, csrc/illumtrain/),
     librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
     the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/),
-    librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/), librobir_hip_photoloss.so (the tone curves' backward
+    and the fused image loss, csrc/photoloss/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -236,6 +240,22 @@ def observe():
 def call_observe(name, *args):
     """An entry point of the observation library."""
     _call_aux(observe(), name, *args)
+
+
+def photoloss():
+    """The photometric-loss library (include/robir_hip_photoloss.h; `make -C robir_amd/csrc photoloss`): the reverse mode of ACESToneMapping's
+    curves and the fused masked image loss with its gradient."""
+    global _photoloss
+    if _photoloss is None:
+        _photoloss = _load_aux(PHOTOLOSS_PATH, PHOTOLOSS_ABI_VERSION, "rb_pl_", ("rb_pl_groups", "rb_pl_scratch_bytes"), "photoloss",
+                               "PHOTOMETRIC-LOSS library librobir_hip_photoloss.so",
+                               "tone-map gradients and the image loss, robir_amd/tonemap_autograd.py")
+    return _photoloss
+
+
+def call_photoloss(name, *args):
+    """An entry point of the photometric-loss library."""
+    _call_aux(photoloss(), name, *args)
 
 
 def legacy_loaded():

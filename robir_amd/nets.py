@@ -966,6 +966,19 @@ class ACESToneMapping(nn.Module):
         shape = x.shape
         rows = x.numel() // 3
         p = self.adapt_illum
+        from . import deferred
+        if getattr(self, "_tonemap_training", False) and torch.is_grad_enabled() and not deferred.is_deferred(x):
+            # robir_amd.training.enable_tonemap_training: the same bits with a graph to x, to a raw_shift tensor and -- raw_shift=None -- to
+            # adapt_illum through as_input().  The cached shift below carries no graph: it neither serves nor is written by this branch.
+            live = self.as_input() if raw_shift is None else raw_shift
+            if x.requires_grad or (isinstance(live, torch.Tensor) and live.requires_grad):
+                from . import tonemap_autograd
+                if not isinstance(live, torch.Tensor):
+                    live = torch.tensor(live, device=x.device)
+                sh = live.float().reshape(-1).to(x.device)
+                if sh.numel() != 1 and sh.numel() != rows:
+                    raise ValueError(f"ACESToneMapping: a shift of {sh.numel()} values for {rows} rows (one value, or one per row)")
+                return tonemap_autograd.tonemap(x.float().reshape(-1, 3), sh, self._curve, mode).reshape(shape)
         key = (p.data_ptr(), p._version, x.device)
         if raw_shift is None and getattr(self, "_shift_key", None) == key:
             sh = self._shift_val               # the model's own shift: ten tiny launches per call otherwise

@@ -1684,3 +1684,76 @@ def ob_gather(index, x, cam_loc, pose_inv, K, images, masks=None):
     _lib.call_observe("rb_ob_gather", nz(index), c_int(n_obs), nz(x), c_long(N), ptr(cam_loc), ptr(pose_inv), ptr(K), c_int(M), ptr(images),
                       None if masks is None else ptr(masks), c_int(H), c_int(W), c_int(C), nz(uv), nz(view_dir), nz(rgb), nz(valid), stream_ptr())
     return uv, view_dir, rgb, valid
+
+
+# ------------------------------------------------------------------------------------------------ photometric loss (librobir_hip_photoloss.so)
+PL_CURVE_IDENTITY, PL_CURVE_RATIONAL = 3, 4
+
+
+def _pl_shift(shift, n, dev):
+    """-> (tensor or None, stride): a single value or one per row."""
+    if shift is None:
+        return None, 0
+    shift = _f32(shift).reshape(-1)
+    if shift.numel() != 1 and shift.numel() != n:
+        raise ValueError(f"photometric loss: the shift has {shift.numel()} values for {n} rows (one, or one per row)")
+    return shift, (0 if shift.numel() == 1 else 1)
+
+
+def _pl_scratch(n, dev):
+    return torch.empty(max(16, int(_lib.photoloss().rb_pl_scratch_bytes(c_long(n)))), dtype=torch.uint8, device=dev)
+
+
+def pl_tonemap(x, shift, curve, inverse=0):
+    """x [n,3], shift [1] | [n] (None for curves 3 / 4) -> y [n,3]: the curve's fp32 forward out of photoloss_math.h (ops.tonemap's bits)."""
+    x = _f32(x)
+    n = x.shape[0]
+    assert tuple(x.shape) == (n, 3)
+    shift, stride = _pl_shift(shift, n, x.device)
+    y = torch.empty_like(x)
+    nz = lambda t: ptr(t) if t is not None and t.numel() else None
+    _lib.call_photoloss("rb_pl_tonemap", nz(x), c_long(n), nz(shift), c_int(stride), c_int(int(curve)), c_int(int(inverse)), nz(y), stream_ptr())
+    return y
+
+
+def pl_tonemap_backward(x, shift, curve, inverse, gy, want_x=True, want_shift=True):
+    """Reverse mode of a tone curve: x, gy [n,3], shift [1] | [n] -> (gx [n,3] or None, gshift like shift or None)."""
+    x, gy = _f32(x), _f32(gy)
+    n, dev = x.shape[0], x.device
+    assert tuple(x.shape) == (n, 3) and tuple(gy.shape) == (n, 3)
+    shift, stride = _pl_shift(shift, n, dev)
+    gx = torch.empty_like(x) if want_x else None
+    gshift = None
+    if want_shift and shift is not None:
+        gshift = torch.zeros(1, dtype=torch.float32, device=dev) if stride == 0 else torch.empty(n, dtype=torch.float32, device=dev)
+    scratch = _pl_scratch(n, dev) if gshift is not None and stride == 0 else None
+    nz = lambda t: ptr(t) if t is not None and t.numel() else None
+    _lib.call_photoloss("rb_pl_tonemap_bwd", nz(x), c_long(n), nz(shift), c_int(stride), c_int(int(curve)), c_int(int(inverse)), nz(gy), nz(gx),
+                        nz(gshift), nz(scratch), c_long(0 if scratch is None else scratch.numel()), stream_ptr())
+    return gx, gshift
+
+
+def pl_image_loss(sg_rgb, indir_rgb, gt, net_mask, obj_mask, shift, curve, l2=False, want_rgb=True, want_shift=True):
+    """The fused image loss: sg_rgb, gt [N,3], indir_rgb [N,3] or None, the masks [N] bool / uint8, shift [1] | [N] | None ->
+    (loss [] fp32, g_rgb [N,3] or None, g_shift like shift or None), the gradients for a unit upstream."""
+    sg_rgb, gt = _f32(sg_rgb), _f32(gt)
+    N, dev = sg_rgb.shape[0], sg_rgb.device
+    assert tuple(sg_rgb.shape) == (N, 3) and tuple(gt.shape) == (N, 3)
+    if indir_rgb is not None:
+        indir_rgb = _f32(indir_rgb)
+        assert tuple(indir_rgb.shape) == (N, 3)
+    m1 = net_mask.reshape(-1).to(torch.uint8).contiguous()
+    m2 = obj_mask.reshape(-1).to(torch.uint8).contiguous()
+    assert m1.numel() == N and m2.numel() == N
+    shift, stride = _pl_shift(shift, N, dev)
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    g_rgb = torch.empty(N, 3, dtype=torch.float32, device=dev) if want_rgb else None
+    g_shift = None
+    if want_shift and shift is not None:
+        g_shift = torch.zeros(1, dtype=torch.float32, device=dev) if stride == 0 else torch.empty(N, dtype=torch.float32, device=dev)
+    scratch = _pl_scratch(N, dev)
+    nz = lambda t: ptr(t) if t is not None and t.numel() else None
+    _lib.call_photoloss("rb_pl_image_loss", nz(sg_rgb), nz(indir_rgb), nz(gt), nz(m1), nz(m2), c_long(N), nz(shift), c_int(stride),
+                        c_int(int(curve)), c_int(1 if l2 else 0), ptr(loss), nz(g_rgb), nz(g_shift), ptr(scratch), c_long(scratch.numel()),
+                        stream_ptr())
+    return loss.reshape(()), g_rgb, g_shift

@@ -25,7 +25,13 @@ indirect_sgs / indir_integral carry it, and radiance_loss restates model/loss.py
 The CESR stage (training/train_cesr.py:107-117: the optimiser holds shadow_net and normal_net): enable_cesr_training marks an SDFNetwork of
 kind shadow or normal.  With the mark, grad mode on and a parameter that requires grad, SDFNetwork.forward / eval_point_labels / diffuse_vis /
 unit_normal return outputs with a graph to the 27 weight-norm tensors (robir_amd/cesr_autograd.py -> librobir_hip_cesrtrain.so), and
-renderer.CESRHook carries it into the shading (diffuse_vis) and into the normal-consistency term of gradient_error (normal_new)."""
+renderer.CESRHook carries it into the shading (diffuse_vis) and into the normal-consistency term of gradient_error (normal_new).
+
+The image loss that drives all of them (model/loss.py:97-125, called by training/train_pbr.py:321 and train_cesr.py:395):
+enable_tonemap_training marks an ACESToneMapping.  With the mark and grad mode on, hdr2ldr / ldr2hdr return the same bits plus a graph to x,
+to a raw_shift tensor and -- raw_shift=None -- to adapt_illum (robir_amd/tonemap_autograd.py -> librobir_hip_photoloss.so);
+photometric_loss is the fused tone map + masked L1 / L2 + gradient, white_loss the runner's light prior; eikonal_loss, mask_loss and
+normal_loss restate the remaining terms of model/loss.py:44-73; robir_amd/loss.py assembles InvLoss / IllumLoss from these pieces."""
 import torch
 
 from . import nets
@@ -182,3 +188,92 @@ def radiance_loss(model_outputs, trace_outputs, anneal_t=0.0, loss_type="L1", qu
     pred_radiance = query(model_outputs["indirect_sgs"][points_mask], trace_outputs["sample_dirs"])
     loss = dist(pred_radiance[indir_mask[points_mask]], gt_radiance)
     return loss + dist(model_outputs["indir_integral"][points_mask], trace_outputs["gt_integral"][points_mask])
+
+
+def _tone_mapper(obj):
+    if isinstance(obj, nets.ACESToneMapping):
+        return obj
+    if isinstance(obj, nets.GammaCorrect):
+        return obj.hdr_shift
+    gamma = getattr(obj, "gamma", None)
+    if isinstance(gamma, nets.GammaCorrect):
+        return gamma.hdr_shift
+    return None
+
+
+def enable_tonemap_training(obj, on=True):
+    """Mark (on=False: unmark) an ACESToneMapping -- or the one a GammaCorrect holds as .hdr_shift, or the one of a model's .gamma -- as
+    differentiable on the HIP path.  Returns the tone mapper.  With the mark and grad mode on, hdr2ldr / ldr2hdr return today's bits plus a
+    graph to x, to a raw_shift tensor and, for raw_shift=None, to adapt_illum (robir_amd/tonemap_autograd.py -> librobir_hip_photoloss.so);
+    a deferred x, no_grad and an unmarked module behave as before."""
+    tone = _tone_mapper(obj)
+    if tone is None:
+        raise TypeError(f"enable_tonemap_training: {type(obj).__name__} is neither an ACESToneMapping, a GammaCorrect nor a model that has .gamma")
+    tone._tonemap_training = bool(on)
+    return tone
+
+
+def tonemap_training_enabled(obj):
+    return bool(getattr(_tone_mapper(obj), "_tonemap_training", False))
+
+
+def photometric_loss(sg_rgb, indir_rgb, rgb_gt, network_object_mask, object_mask, tone=None, raw_shift=None, loss_type="L1"):
+    """The image term of InvLoss.forward (model/loss.py:31-42,97-110) as ONE fused, differentiable op: with m = network_object_mask &
+    object_mask [N] and pred = tone.hdr2ldr(sg_rgb + indir_rgb, raw_shift), sum_m sum_c |pred - rgb_gt| (loss_type "L2": squared) / N, N all
+    rows.  indir_rgb may be None.  tone: an ACESToneMapping (or what enable_tonemap_training accepts); None gives the reference's fallback
+    pred = x / (x + 1).  Gradients reach sg_rgb and indir_rgb, and -- only for a tone marked by enable_tonemap_training -- a raw_shift
+    tensor or, for raw_shift=None, adapt_illum through as_input(); an unmarked tone is a constant curve."""
+    from . import ops, tonemap_autograd
+    if loss_type not in ("L1", "L2"):
+        raise ValueError(f"photometric_loss: unknown loss_type {loss_type!r} (L1 | L2)")
+    shift, curve = None, ops.PL_CURVE_RATIONAL
+    if tone is not None:
+        tm = _tone_mapper(tone)
+        if tm is None:
+            raise TypeError(f"photometric_loss: tone is a {type(tone).__name__}, not an ACESToneMapping")
+        curve = tm._curve
+        if curve != ops.PL_CURVE_IDENTITY:
+            marked = tonemap_training_enabled(tm) and torch.is_grad_enabled()
+            shift = tm.as_input() if raw_shift is None else raw_shift
+            if not isinstance(shift, torch.Tensor):
+                shift = torch.tensor(float(shift), device=sg_rgb.device)
+            shift = shift.to(sg_rgb.device).float()
+            if not marked:
+                shift = shift.detach()
+    return tonemap_autograd.image_loss(sg_rgb, indir_rgb, rgb_gt.to(sg_rgb.device), network_object_mask, object_mask, shift, curve,
+                                       l2=loss_type == "L2")
+
+
+def white_loss(lgtSGs):
+    """The white-light prior of the stage-3 runner (training/train_pbr.py:313-316) on tensors: 0.01 times the mean over the lobes of the
+    variance of |mu| / (|mu|_2 + 1e-4) across the three channels."""
+    lgt = torch.abs(lgtSGs[..., -3:])
+    mu = lgt.norm(dim=-1, keepdim=True) + 1e-4
+    return (lgt / mu).var(-1).mean() * 0.01
+
+
+def eikonal_loss(grad_theta):
+    """The eikonal term (model/loss.py:44-49): mean over the rows of (|grad_theta|_2 - 1)^2 for SDF gradients [n,3]; 0 for n = 0."""
+    if grad_theta.shape[0] == 0:
+        return torch.zeros((), dtype=torch.float32, device=grad_theta.device)
+    length = torch.linalg.vector_norm(grad_theta, ord=2, dim=1)
+    return torch.mean(torch.square(length - 1.0))
+
+
+def mask_loss(sdf_output, network_object_mask, object_mask, alpha):
+    """The silhouette term (model/loss.py:51-59).  Over the rows OUTSIDE network_object_mask & object_mask, the summed binary cross entropy
+    between the logits -alpha * sdf and the target object_mask, divided by alpha and by the number N of all rows; 0 if there is no such row."""
+    outside = torch.logical_not(torch.logical_and(network_object_mask, object_mask))
+    if not bool(outside.any()):
+        return torch.zeros((), dtype=torch.float32, device=sdf_output.device)
+    logits = (sdf_output[outside] * (-alpha)).squeeze()
+    target = object_mask[outside].to(logits.dtype)
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(logits, target, reduction="sum")
+    return bce / (alpha * float(object_mask.shape[0]))
+
+
+def normal_loss(normal_map, normals, surface_mask):
+    """The normal term (model/loss.py:69-73): the mean squared difference between the predicted normal map and the geometry's normals over
+    the rows of surface_mask."""
+    keep = surface_mask.reshape(-1).bool()
+    return torch.nn.functional.mse_loss(normal_map.reshape(-1, normal_map.shape[-1])[keep], normals.reshape(-1, normals.shape[-1])[keep])
