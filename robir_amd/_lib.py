@@ -51,6 +51,9 @@ OBSERVE_ABI_VERSION = 1
 PHOTOLOSS_PATH = os.path.join(_HERE, "librobir_hip_photoloss.so")
 _photoloss = None
 PHOTOLOSS_ABI_VERSION = 1
+METRICS_PATH = os.path.join(_HERE, "librobir_hip_metrics.so")
+_metrics = None
+METRICS_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -60,7 +63,7 @@ def build(verbose=False, legacy=True):
     librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
     the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/),
     librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/), librobir_hip_photoloss.so (the tone curves' backward
-    and the fused image loss, csrc/photoloss/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    and the fused image loss, csrc/photoloss/), librobir_hip_metrics.so (PSNR / SSIM / normal error / albedo ratio, csrc/metrics/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -256,6 +259,23 @@ def photoloss():
 def call_photoloss(name, *args):
     """An entry point of the photometric-loss library."""
     _call_aux(photoloss(), name, *args)
+
+
+def metrics():
+    """The metrics library (include/robir_hip_metrics.h; `make -C robir_amd/csrc metrics`): the fp64 sums behind MSE / MAE / PSNR / the albedo
+    ratio, the angular error of two normal fields and SSIM, V views per launch."""
+    global _metrics
+    if _metrics is None:
+        _metrics = _load_aux(METRICS_PATH, METRICS_ABI_VERSION, "rb_mt_",
+                             ("rb_mt_groups", "rb_mt_ssim_tiles", "rb_mt_pair_scratch_bytes", "rb_mt_angular_scratch_bytes",
+                              "rb_mt_ssim_scratch_bytes"), "metrics", "METRICS library librobir_hip_metrics.so",
+                             "PSNR, SSIM, normal error and albedo ratio of rendered views, robir_amd/metrics.py")
+    return _metrics
+
+
+def call_metrics(name, *args):
+    """An entry point of the metrics library."""
+    _call_aux(metrics(), name, *args)
 
 
 def legacy_loaded():

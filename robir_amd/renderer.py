@@ -137,6 +137,11 @@ class IDRNetwork(nn.Module):
         mat = self.envmap_material_network(points, train_spec=True,
                                            noise={"spec": draws.get("spec_randn"), "normal": draws.get("normal_randn")})
         shading_normal = normals if self.no_normal else mat["sg_normal_map"]
+        if albedo_ratio is not None:
+            # the class default of the reference (implicit_differentiable_renderer.py:508-509): the albedo aligned to ground truth before it
+            # is shaded and returned (robir_amd.metrics.albedo_ratio computes the factor).  None: nothing changes.
+            mat["sg_diffuse_albedo"] = mat["sg_diffuse_albedo"] * torch.as_tensor(albedo_ratio, dtype=torch.float32,
+                                                                                  device=points.device).reshape(1, 3)
         ret = sg_render.render_with_all_sg(points=points, normal=shading_normal, viewdirs=vd, lgtSGs=mat["sg_lgtSGs"],
                                            indir_integral=ops.abs_scale(indir_integral, 2 * np.pi, take_abs=False),
                                            specular_reflectance=mat["sg_specular_reflectance"].abs(),
