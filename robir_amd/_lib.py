@@ -54,6 +54,9 @@ PHOTOLOSS_ABI_VERSION = 1
 METRICS_PATH = os.path.join(_HERE, "librobir_hip_metrics.so")
 _metrics = None
 METRICS_ABI_VERSION = 1
+RASTER_PATH = os.path.join(_HERE, "librobir_hip_raster.so")
+_raster = None
+RASTER_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -63,7 +66,8 @@ def build(verbose=False, legacy=True):
     librobir_hip_cesrtrain.so (the backward of the CESR stage's shadow_net / normal_net, csrc/cesrtrain/), librobir_hip_lightfit.so (the fit of
     the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/),
     librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/), librobir_hip_photoloss.so (the tone curves' backward
-    and the fused image loss, csrc/photoloss/), librobir_hip_metrics.so (PSNR / SSIM / normal error / albedo ratio, csrc/metrics/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    and the fused image loss, csrc/photoloss/), librobir_hip_metrics.so (PSNR / SSIM / normal error / albedo ratio, csrc/metrics/),
+    librobir_hip_raster.so (the camera-space rasteriser and the G-buffer, csrc/raster/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -276,6 +280,21 @@ def metrics():
 def call_metrics(name, *args):
     """An entry point of the metrics library."""
     _call_aux(metrics(), name, *args)
+
+
+def raster():
+    """The rasteriser library (include/robir_hip_raster.h; `make -C robir_amd/csrc raster`): the projection of a mesh's vertices, tile binning,
+    the camera-space rasteriser with its depth test and the G-buffer with its plane fetch."""
+    global _raster
+    if _raster is None:
+        _raster = _load_aux(RASTER_PATH, RASTER_ABI_VERSION, "rb_rs_", (), "raster", "RASTERISER library librobir_hip_raster.so",
+                            "views of a baked mesh, robir_amd/meshrender.py")
+    return _raster
+
+
+def call_raster(name, *args):
+    """An entry point of the rasteriser library."""
+    _call_aux(raster(), name, *args)
 
 
 def legacy_loaded():

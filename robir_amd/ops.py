@@ -1757,3 +1757,116 @@ def pl_image_loss(sg_rgb, indir_rgb, gt, net_mask, obj_mask, shift, curve, l2=Fa
                         c_int(int(curve)), c_int(1 if l2 else 0), ptr(loss), nz(g_rgb), nz(g_shift), ptr(scratch), c_long(scratch.numel()),
                         stream_ptr())
     return loss.reshape(()), g_rgb, g_shift
+
+
+# ------------------------------------------------------------------------------------------------ camera-space rasteriser (librobir_hip_raster.so)
+RS_TILE, RS_MAX_RESOLUTION, RS_MAX_CHANNELS = 8, 16384, 16
+
+
+def _rs_mesh(screen, faces):
+    screen = _f32(screen)
+    if screen.dim() != 2 or screen.shape[1] != 4 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"rasteriser: screen must be [V,4] and faces [F,3], got {tuple(screen.shape)}, {tuple(faces.shape)}")
+    assert faces.dtype == torch.int32 and faces.is_contiguous()
+    return screen
+
+
+def _rs_image(H, W):
+    H, W = int(H), int(W)
+    if not (1 <= H <= RS_MAX_RESOLUTION and 1 <= W <= RS_MAX_RESOLUTION):
+        raise ValueError(f"rasteriser: image {H} x {W} outside 1 .. {RS_MAX_RESOLUTION} per side")
+    return H, W
+
+
+def rs_project(vertices, pose_inv, K):
+    """vertices [V,3], pose_inv [4,4] (the inverse of the camera-to-world pose), K [3,3] -> screen [V,4] = (u, v, 1 / zc, zc)."""
+    vertices, pose_inv, K = _f32(vertices), _f32(pose_inv), _f32(K)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or tuple(pose_inv.shape) != (4, 4) or tuple(K.shape) != (3, 3):
+        raise ValueError(f"rasteriser: vertices [V,3], pose_inv [4,4], K [3,3], got {tuple(vertices.shape)}, {tuple(pose_inv.shape)}, "
+                         f"{tuple(K.shape)}")
+    V = vertices.shape[0]
+    screen = torch.empty(V, 4, dtype=torch.float32, device=vertices.device)
+    if V:
+        _lib.call_raster("rb_rs_project", ptr(vertices), c_long(V), ptr(pose_inv), ptr(K), ptr(screen), stream_ptr())
+    return screen
+
+
+def rs_bin_count(screen, faces, H, W, near, cull):
+    """-> counts [F] int32: tiles of 8 x 8 pixels each face's pixel box touches (0: a skipped face)."""
+    screen = _rs_mesh(screen, faces)
+    H, W = _rs_image(H, W)
+    nz = lambda t: ptr(t) if t.numel() else None
+    counts = torch.empty(faces.shape[0], dtype=torch.int32, device=screen.device)
+    _lib.call_raster("rb_rs_bin_count", nz(screen), c_long(screen.shape[0]), nz(faces), c_long(faces.shape[0]), c_int(H), c_int(W),
+                     c_float(near), c_int(int(cull)), nz(counts), stream_ptr())
+    return counts
+
+
+def rs_bin_emit(screen, faces, H, W, near, cull, base, P):
+    """base [F] int64 exclusive prefix of the counts, P their total -> (pair_tile [P], pair_face [P]) int32 in face order."""
+    screen = _rs_mesh(screen, faces)
+    H, W = _rs_image(H, W)
+    assert base.dtype == torch.int64 and base.is_contiguous() and base.numel() == faces.shape[0]
+    pair_tile = torch.empty(P, dtype=torch.int32, device=screen.device)
+    pair_face = torch.empty(P, dtype=torch.int32, device=screen.device)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_raster("rb_rs_bin_emit", nz(screen), c_long(screen.shape[0]), nz(faces), c_long(faces.shape[0]), c_int(H), c_int(W),
+                     c_float(near), c_int(int(cull)), nz(base), c_long(P), nz(pair_tile), nz(pair_face), stream_ptr())
+    return pair_tile, pair_face
+
+
+def rs_raster(screen, faces, H, W, near, cull, tile_start, pair_face):
+    """-> (face_id [H,W] int32, bary [H,W,2], depth [H,W])."""
+    screen = _rs_mesh(screen, faces)
+    H, W = _rs_image(H, W)
+    ntiles = ((W + RS_TILE - 1) // RS_TILE) * ((H + RS_TILE - 1) // RS_TILE)
+    assert tile_start.dtype == torch.int32 and tile_start.numel() == ntiles + 1 and pair_face.dtype == torch.int32
+    assert tile_start.is_contiguous() and pair_face.is_contiguous()
+    dev = screen.device
+    face_id = torch.empty(H, W, dtype=torch.int32, device=dev)
+    bary = torch.empty(H, W, 2, dtype=torch.float32, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    nz = lambda t: ptr(t) if t.numel() else None
+    _lib.call_raster("rb_rs_raster", nz(screen), c_long(screen.shape[0]), nz(faces), c_long(faces.shape[0]), c_int(H), c_int(W), c_float(near),
+                     c_int(int(cull)), ptr(tile_start), nz(pair_face), c_long(pair_face.numel()), ptr(face_id), ptr(bary), ptr(depth),
+                     stream_ptr())
+    return face_id, bary, depth
+
+
+def rs_gbuffer(face_id, bary, faces, vertices, uv, cam_loc, planes=None, filter=1, vnormals=None, index=None):
+    """The G-buffer of the pixels of face_id / bary [H,W] (index None: all, rows [H W, .]) or of the flat pixel indices index [n] int64 ->
+    (position [n,3], uv [n,2], view_dir [n,3], tex [n,C] or None, normal [n,3] or None).  faces [F,3] int32, vertices [V,3], uv [F,3,2],
+    cam_loc [3], planes [R,R,C] or None, vnormals [V,3] or None."""
+    assert face_id.dtype == torch.int32 and face_id.is_contiguous() and face_id.dim() == 2 and faces.dtype == torch.int32
+    bary, vertices, uv, cam_loc, faces = _f32(bary), _f32(vertices), _f32(uv), _f32(cam_loc).reshape(-1), faces.contiguous()
+    H, W = face_id.shape
+    F, V, dev = faces.shape[0], vertices.shape[0], face_id.device
+    if tuple(bary.shape) != (H, W, 2) or tuple(faces.shape) != (F, 3) or tuple(vertices.shape) != (V, 3) or tuple(uv.shape) != (F, 3, 2) \
+            or cam_loc.numel() != 3:
+        raise ValueError(f"gbuffer: bary [H,W,2], faces [F,3], vertices [V,3], uv [F,3,2], cam_loc [3], got {tuple(bary.shape)}, "
+                         f"{tuple(faces.shape)}, {tuple(vertices.shape)}, {tuple(uv.shape)}, {tuple(cam_loc.shape)}")
+    R = C = 0
+    if planes is not None:
+        planes = _f32(planes)
+        if planes.dim() != 3 or planes.shape[0] != planes.shape[1] or not 1 <= planes.shape[2] <= RS_MAX_CHANNELS:
+            raise ValueError(f"gbuffer: planes must be [R,R,C] with C <= {RS_MAX_CHANNELS}, got {tuple(planes.shape)}")
+        R, C = planes.shape[0], planes.shape[2]
+    if vnormals is not None:
+        vnormals = _f32(vnormals)
+        if tuple(vnormals.shape) != (V, 3):
+            raise ValueError(f"gbuffer: vnormals must be [V,3] = {(V, 3)}, got {tuple(vnormals.shape)}")
+    if index is None:
+        n = H * W
+    else:
+        assert index.dtype == torch.int64 and index.is_contiguous()
+        n = index.numel()
+    new = lambda c: torch.empty(n, c, dtype=torch.float32, device=dev)
+    position, uv_out, view_dir = new(3), new(2), new(3)
+    tex = new(C) if planes is not None else None
+    normal = new(3) if vnormals is not None else None
+    nz = lambda t: ptr(t) if t is not None and t.numel() else None
+    if n:
+        _lib.call_raster("rb_rs_gbuffer", ptr(face_id), ptr(bary), c_int(H), c_int(W), None if index is None else ptr(index), c_long(n),
+                         nz(faces), c_long(F), nz(vertices), c_long(V), nz(uv), nz(vnormals), ptr(cam_loc), nz(planes), c_int(R), c_int(C),
+                         c_int(int(filter)), ptr(position), ptr(uv_out), ptr(view_dir), nz(tex), nz(normal), stream_ptr())
+    return position, uv_out, view_dir, tex, normal

@@ -287,7 +287,7 @@ def render_with_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, rough
         lgt_first = (lgtSGs if lgtSGs.dim() == 2 else lgtSGs[0]).float().contiguous()
     light_vis = None
     supervise = torch.zeros((), device=dev)
-    if comp_vis:
+    if comp_vis and VisModel is not None:          # VisModel None: direct shading, every light and every BRDF lobe unoccluded
         nsamp = 32 if diffuse_vis is None else 8          # sg_render.py:389
         u_t = draws.get("dvis_theta")
         u_p = draws.get("dvis_phi")
@@ -315,6 +315,8 @@ def render_with_sg(points, normal, viewdirs, lgtSGs, specular_reflectance, rough
                             indir_integral=indir_integral, lin_diff=lin_diff, want_shadow=True)
 
     def shade(rough_, spec_draws):
+        if VisModel is None:
+            return sg_shade(rough_, torch.ones(n, device=dev))
         u_t, u_p = spec_draws.get("svis_theta"), spec_draws.get("svis_phi")
         if u_t is None:
             u_t, u_p = _rand((n, 8), dev), _rand((n, 8), dev)
