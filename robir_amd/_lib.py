@@ -57,6 +57,9 @@ METRICS_ABI_VERSION = 1
 RASTER_PATH = os.path.join(_HERE, "librobir_hip_raster.so")
 _raster = None
 RASTER_ABI_VERSION = 1
+TEXFIT_PATH = os.path.join(_HERE, "librobir_hip_texfit.so")
+_texfit = None
+TEXFIT_ABI_VERSION = 1
 
 
 def build(verbose=False, legacy=True):
@@ -67,7 +70,8 @@ def build(verbose=False, legacy=True):
     the light SGs to an environment map, csrc/lightfit/), librobir_hip_texbake.so (baking into texture space, csrc/texbake/),
     librobir_hip_observe.so (multi-view observations of surface points, csrc/observe/), librobir_hip_photoloss.so (the tone curves' backward
     and the fused image loss, csrc/photoloss/), librobir_hip_metrics.so (PSNR / SSIM / normal error / albedo ratio, csrc/metrics/),
-    librobir_hip_raster.so (the camera-space rasteriser and the G-buffer, csrc/raster/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
+    librobir_hip_raster.so (the camera-space rasteriser and the G-buffer, csrc/raster/), librobir_hip_texfit.so (the fit of a baked atlas
+    to views, csrc/texfit/) and -- legacy=True -- librobir_hip_legacy.so (the superset with the retired kernel
     generations, csrc/Makefile)."""
     # MAX_JOBS where the environment sets the build's share of the CPUs (os.cpu_count() is the whole machine's); never above 16
     jobs = str(max(1, min(16, int(os.environ.get("MAX_JOBS") or min(8, os.cpu_count() or 1)))))
@@ -295,6 +299,21 @@ def raster():
 def call_raster(name, *args):
     """An entry point of the rasteriser library."""
     _call_aux(raster(), name, *args)
+
+
+def texfit():
+    """The atlas-fitting library (include/robir_hip_texfit.h; `make -C robir_amd/csrc texfit`): the taps that linearise the mesh view's plane
+    fetch, the fetch formed from them, its transpose as a gather and lazy Adam on the touched texels."""
+    global _texfit
+    if _texfit is None:
+        _texfit = _load_aux(TEXFIT_PATH, TEXFIT_ABI_VERSION, "rb_tf_", (), "texfit", "ATLAS-FITTING library librobir_hip_texfit.so",
+                            "fitting a baked atlas to views, robir_amd/texfit.py")
+    return _texfit
+
+
+def call_texfit(name, *args):
+    """An entry point of the atlas-fitting library."""
+    _call_aux(texfit(), name, *args)
 
 
 def legacy_loaded():

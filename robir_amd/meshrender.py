@@ -12,7 +12,8 @@ DESIGN 4.13).  The hit rows are shaded by the existing sg_render.render_with_all
 
 Conventions: the renderer's camera (looks along -z, y up; pose is camera-to-world, 4 x 4 or the 7-vector form); the sample point of pixel
 (row r, column c) is (u, v) = (c, r), the integer uv grid of synth.synth_camera / render.blender_camera.  No clipping: a face with a corner
-behind the near plane is skipped whole, so a camera INSIDE the object is out of scope.  Everything runs under no_grad.
+behind the near plane is skipped whole, so a camera INSIDE the object is out of scope.  Everything here runs under no_grad; robir_amd.texfit
+takes the gradient of this view with respect to the albedo and roughness texels and fits them to target views.
 """
 import argparse
 import os
@@ -151,6 +152,19 @@ def _rows(draws, idx, n_pixels):
                 else v) for k, v in (draws or {}).items()}
 
 
+def light_and_f0(model, light, dev):
+    """(light SGs [M,7], specular_reflectance) a view is shaded under: those of `light` ([M,7] or a directory with sg_128.npy; it overrides
+    the model's) or of `model`; f0 = 0.02 without a model.  Detached: constants of whoever shades with them."""
+    with torch.no_grad():
+        if light is not None:
+            lgt = light.to(dev).float().contiguous() if torch.is_tensor(light) else load_light(light, dev)
+        else:
+            mn = model.envmap_material_network
+            lgt = (mn.restrict_lobes_upper(mn.lgtSGs) if mn.upper_hemi else mn.lgtSGs).detach()
+        f0 = model.envmap_material_network.specular_reflectance.detach().abs() if model is not None else torch.full((1, 1), 0.02, device=dev)
+    return lgt, f0
+
+
 def shade_rows(points, normal, view_dir, albedo, roughness, model=None, light=None, vis="none", draws=None):
     """sg_render.render_with_all_sg on n surface rows with materials given per row (points, normal, view_dir, albedo [n,3], roughness [n,1]),
     under the lights and specular_reflectance of `model` or of `light` ([M,7] or a directory with sg_128.npy; it overrides the model's) ->
@@ -159,12 +173,7 @@ def shade_rows(points, normal, view_dir, albedo, roughness, model=None, light=No
     dev, n = points.device, points.shape[0]
     d = draws or {}
     with torch.no_grad():
-        if light is not None:
-            lgt = light.to(dev).float().contiguous() if torch.is_tensor(light) else load_light(light, dev)
-        else:
-            mn = model.envmap_material_network
-            lgt = (mn.restrict_lobes_upper(mn.lgtSGs) if mn.upper_hemi else mn.lgtSGs).detach()
-        f0 = model.envmap_material_network.specular_reflectance.detach().abs() if model is not None else torch.full((1, 1), 0.02, device=dev)
+        lgt, f0 = light_and_f0(model, light, dev)
         indir_sgs = indir_int = vis_model = None
         if vis != "none":
             from .octree_tracing import OctreeVisModel
@@ -175,6 +184,20 @@ def shade_rows(points, normal, view_dir, albedo, roughness, model=None, light=No
         return sg_render.render_with_all_sg(points=points, normal=normal, viewdirs=view_dir, lgtSGs=lgt, specular_reflectance=f0,
                                             roughness=roughness, diffuse_albedo=albedo, indir_integral=indir_int, indir_lgtSGs=indir_sgs,
                                             VisModel=vis_model, testing=bool(getattr(model, "testing", True)), metallic=None, draws=d)
+
+
+def view_rows(a, pose, K, H, W, filter=1, near=1e-4, cull=0):
+    """The per-view setup that render_mesh and robir_amd.texfit share: the MeshAsset `a` projected, rasterised and its G-buffer formed for the
+    hit rows -> (face_id [H,W] int32, depth [H,W], hit [H W] bool, idx [n] int64: the flat hit pixels, g: gbuffer's dict for those rows --
+    position, uv, view_dir, tex from all of a.planes, and normal from the vertex normals for an asset without a normal plane)."""
+    with torch.no_grad():
+        pinv, cam = pose_inverse(pose)
+        screen = ops.rs_project(a.vertices, pinv, K[:3, :3])
+        face_id, bary, depth = rasterize_screen(screen, a.faces, H, W, near, cull)
+        hit = face_id.reshape(-1) >= 0
+        idx = hit.nonzero()[:, 0].contiguous()
+        g = gbuffer(face_id, bary, a.vertices, a.faces, a.uv, cam, a.planes, filter, None if a.has_normal else a.vnormals, idx)
+    return face_id, depth, hit, idx, g
 
 
 def render_mesh(asset, pose, K, H, W, model=None, light=None, vis="none", filter=1, draws=None, near=1e-4, cull=0):
@@ -203,13 +226,8 @@ def render_mesh(asset, pose, K, H, W, model=None, light=None, vis="none", filter
     N = H * W
     pose, K = torch.as_tensor(pose).to(dev).float(), torch.as_tensor(K).to(dev).float()
     with torch.no_grad():
-        pinv, cam = pose_inverse(pose)
-        screen = ops.rs_project(a.vertices, pinv, K[:3, :3])
-        face_id, bary, depth = rasterize_screen(screen, a.faces, H, W, near, cull)
-        hit = face_id.reshape(-1) >= 0
-        idx = hit.nonzero()[:, 0].contiguous()
+        face_id, depth, hit, idx, g = view_rows(a, pose, K, H, W, filter, near, cull)
         n = idx.numel()
-        g = gbuffer(face_id, bary, a.vertices, a.faces, a.uv, cam, a.planes, filter, None if a.has_normal else a.vnormals, idx)
         out = {k: torch.ones(N, 3, device=dev) for k in ("sg_rgb", "diffuse_albedo", "roughness", "vis_shadow", "normals", "normal_map",
                                                          "bg_rgb", "points")}
         out.update(metallic=torch.ones(N, 1, device=dev), indir_rgb=torch.zeros(N, 3, device=dev), network_object_mask=hit,

@@ -1870,3 +1870,81 @@ def rs_gbuffer(face_id, bary, faces, vertices, uv, cam_loc, planes=None, filter=
                          nz(faces), c_long(F), nz(vertices), c_long(V), nz(uv), nz(vnormals), ptr(cam_loc), nz(planes), c_int(R), c_int(C),
                          c_int(int(filter)), ptr(position), ptr(uv_out), ptr(view_dir), nz(tex), nz(normal), stream_ptr())
     return position, uv_out, view_dir, tex, normal
+
+
+# ------------------------------------------------------------------------------------------------ atlas fit (librobir_hip_texfit.so)
+TF_MAX_RESOLUTION, TF_MAX_CHANNELS, TF_MAX_ROWS = 16384, 16, 2 ** 29 - 1
+
+
+def _tf_atlas(planes, C=None):
+    """planes [R,R,Cs] -> (R, Cs, C): the resolution, the stack's channels and the leading channels a call works on."""
+    if planes.dim() != 3 or planes.shape[0] != planes.shape[1] or not 1 <= planes.shape[2] <= TF_MAX_CHANNELS:
+        raise ValueError(f"atlas fit: planes must be [R,R,Cs] with Cs <= {TF_MAX_CHANNELS}, got {tuple(planes.shape)}")
+    R, Cs = planes.shape[0], planes.shape[2]
+    C = Cs if C is None else int(C)
+    if not 1 <= R <= TF_MAX_RESOLUTION or not 1 <= C <= Cs:
+        raise ValueError(f"atlas fit: R = {R} outside 1 .. {TF_MAX_RESOLUTION} or C = {C} outside 1 .. Cs = {Cs}")
+    assert planes.dtype == torch.float32 and planes.is_contiguous()
+    return R, Cs, C
+
+
+def tf_taps(uv, R, filter=1):
+    """uv [n,2] -> (tap_texel [n,4] int32, tap_weight [n,4]): the four taps nw, ne, sw, se of the mesh view's plane fetch at uv on an R x R
+    atlas; texel -1 and weight +0 for a tap outside the image.  filter 0: one tap of weight 1 at the containing texel."""
+    uv = _f32(uv)
+    n = uv.shape[0]
+    if uv.dim() != 2 or uv.shape[1] != 2 or n > TF_MAX_ROWS or not 1 <= int(R) <= TF_MAX_RESOLUTION:
+        raise ValueError(f"atlas fit: uv must be [n,2] with n < 2^29 and 1 <= R <= {TF_MAX_RESOLUTION}, got {tuple(uv.shape)}, R = {R}")
+    texel = torch.empty(n, 4, dtype=torch.int32, device=uv.device)
+    weight = torch.empty(n, 4, dtype=torch.float32, device=uv.device)
+    if n:
+        _lib.call_texfit("rb_tf_taps", ptr(uv), c_long(n), c_int(int(R)), c_int(int(filter)), ptr(texel), ptr(weight), stream_ptr())
+    return texel, weight
+
+
+def tf_fetch(planes, tap_texel, tap_weight, C=None):
+    """planes [R,R,Cs], the taps of tf_taps -> tex [n,C]: ((a w0 + b w1) + c w2) + d w3 over the first C channels."""
+    R, Cs, C = _tf_atlas(planes, C)
+    n = tap_texel.shape[0]
+    assert tap_texel.dtype == torch.int32 and tap_texel.is_contiguous() and tuple(tap_texel.shape) == (n, 4)
+    assert tap_weight.dtype == torch.float32 and tap_weight.is_contiguous() and tuple(tap_weight.shape) == (n, 4)
+    tex = torch.empty(n, C, dtype=torch.float32, device=planes.device)
+    if n:
+        _lib.call_texfit("rb_tf_fetch", ptr(planes), c_int(R), c_int(Cs), ptr(tap_texel), ptr(tap_weight), c_long(n), c_int(C), ptr(tex),
+                         stream_ptr())
+    return tex
+
+
+def tf_scatter(pair_row, pair_weight, seg_start, g_tex):
+    """The transpose of tf_fetch as a gather: pair_row [P] int32, pair_weight [P] (the pairs sorted by texel, stable), seg_start [T+1] int32,
+    g_tex [n,C] -> grad [T,C], the fp64 sum over each segment's pairs in ascending order, rounded once."""
+    g_tex = _f32(g_tex)
+    n, C = g_tex.shape
+    P, T = pair_row.numel(), seg_start.numel() - 1
+    assert pair_row.dtype == torch.int32 and pair_row.is_contiguous() and seg_start.dtype == torch.int32 and seg_start.is_contiguous()
+    assert pair_weight.dtype == torch.float32 and pair_weight.is_contiguous() and pair_weight.numel() == P and T >= 0
+    if not 1 <= C <= TF_MAX_CHANNELS:
+        raise ValueError(f"atlas fit: g_tex must be [n,C] with C <= {TF_MAX_CHANNELS}, got {tuple(g_tex.shape)}")
+    grad = torch.empty(T, C, dtype=torch.float32, device=g_tex.device)
+    if T and P:
+        _lib.call_texfit("rb_tf_scatter", ptr(pair_row), ptr(pair_weight), c_long(P), ptr(seg_start), c_long(T), ptr(g_tex), c_long(n),
+                         c_int(C), ptr(grad), stream_ptr())
+    return grad
+
+
+def tf_adam(planes, adam_m, adam_v, seg_texel, grad, lr, lo, hi, beta1, beta2, eps, step):
+    """One lazy Adam step, in place, on the texels seg_texel [T] int32 (no texel twice) of the first C channels of planes [R,R,Cs]: adam_m,
+    adam_v [R,R,C], grad [T,C]; lr, lo, hi: C floats each (step size and clamp per channel); step: the step number t >= 1, whose bias
+    corrections 1 - beta^t are formed here in double."""
+    T, C = grad.shape
+    R, Cs, C = _tf_atlas(planes, C)
+    assert tuple(adam_m.shape) == (R, R, C) and tuple(adam_v.shape) == (R, R, C) and adam_m.is_contiguous() and adam_v.is_contiguous()
+    assert adam_m.dtype == torch.float32 and adam_v.dtype == torch.float32 and grad.dtype == torch.float32 and grad.is_contiguous()
+    assert seg_texel.dtype == torch.int32 and seg_texel.is_contiguous() and seg_texel.numel() == T and int(step) >= 1
+    arr = lambda a: (ctypes.c_double * C)(*[float(x) for x in a])
+    if not (len(lr) == len(lo) == len(hi) == C):
+        raise ValueError(f"atlas fit: lr, lo, hi need {C} values each")
+    if T:
+        _lib.call_texfit("rb_tf_adam", ptr(planes), ptr(adam_m), ptr(adam_v), ptr(seg_texel), ptr(grad), c_long(T), c_int(R), c_int(Cs),
+                         c_int(C), arr(lr), arr(lo), arr(hi), ctypes.c_double(beta1), ctypes.c_double(beta2), ctypes.c_double(eps),
+                         ctypes.c_double(1.0 - float(beta1) ** int(step)), ctypes.c_double(1.0 - float(beta2) ** int(step)), stream_ptr())
